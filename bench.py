@@ -267,6 +267,32 @@ def cpu_baseline():
                        f"torch-CPU fp32 oracle, {cores} threads, {' / '.join(f'{t:.1f}' for t in times)} s per step")
 
 
+DUMP_MAX_ELEMS = 1 << 20   # per array (4 MB as float32): larger outputs are dumped as a fixed, seeded sample of their elements
+
+
+def dump_outputs(out_dir: str, learner, losses) -> dict:
+    """What the last timed update step handed its caller (the reference's ``_update_step`` returns the new parameters and optimiser
+    states with the episode metrics and the loss info), as ``out_dir/<name>.npy`` in float32.  An array of more than DUMP_MAX_ELEMS
+    elements is written as the elements at a fixed, sorted set of flat indices drawn with seed 0, the same for equal shapes, so that
+    two builds run with the same arguments can be compared file by file.  Returns {name: [shape of the full array, sampled]}."""
+    arrays = {"losses": losses, "guider_params": learner.guider.P.flat, "actor_params": learner.actor.P.flat,
+              "guider_adam_mu": learner.g_opt.mu, "guider_adam_nu": learner.g_opt.nu,
+              "actor_adam_mu": learner.a_opt.mu, "actor_adam_nu": learner.a_opt.nu}
+    arrays.update({f"metrics_{k}": v for k, v in learner.metrics.items()})
+    os.makedirs(out_dir, exist_ok=True)
+    info = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        flat = a.reshape(-1)
+        sampled = flat.size > DUMP_MAX_ELEMS
+        if sampled:
+            idx = np.sort(np.random.default_rng(0).choice(flat.size, DUMP_MAX_ELEMS, replace=False))
+            a = flat[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        info[name] = [list(t.shape), sampled]
+    return info
+
+
 def launch_ranks(n: int) -> int:
     """Start ``n`` ranks of this script under torch.distributed.run (one process per GPU, rendezvous on 127.0.0.1) as a child of
     this GPU-free process; forward their stderr, relay rank 0's ONE JSON line from stdout.  Returns the exit status."""
@@ -327,7 +353,11 @@ def main():
                     "instead of bf16 MFMA with three-piece operand splits")
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default nccl = RCCL; gloo only to rehearse ranks on one GPU)")
     ap.add_argument("--check-replicas", action="store_true", help="assert that parameters stayed identical on all ranks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed update step computed "
+                    "(losses, parameters, Adam moments, episode metrics; large arrays as a fixed seeded sample) as DIR/<name>.npy in float32 (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without an outer launcher: this process has not touched the GPU (importing torch does not) and
@@ -455,11 +485,14 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        learner.update_step(sync)
+        losses = learner.update_step(sync)
     barrier()
     elapsed = time.perf_counter() - t0
     timer.enabled = False
     lib().timer = None
+    if args.dump_outputs and rank == 0:   # before the variant measurements below, which train the same learner further
+        dumped = dump_outputs(args.dump_outputs, learner, losses)
+        log(f"dumped {len(dumped)} outputs of the last timed step to {args.dump_outputs}")
     elapsed = reduce_max(elapsed)
     ar_ms = sum(e0.elapsed_time(e1) for e0, e1 in ar_events) / max(1, args.steps) if ar_events else 0.0
     ar_all = None

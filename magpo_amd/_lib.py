@@ -56,6 +56,9 @@ class _Lib:
             raise ImportError(
                 f"{LIB_PATH} not found: the MAGPO HIP library is required (no CPU fallback). "
                 "Build it with `python -c 'import __graft_entry__ as g; g.build()'`.")
+        # torch first: it bundles its own HIP / HSA runtimes under the same sonames, so the library then binds to those.  Loaded
+        # before torch, the library pulls in the system runtimes and torch a second copy, and the library sees no device.
+        import torch  # noqa: F401
         self._dll = ctypes.CDLL(LIB_PATH)
         self.protos = parse_header()
         self._dll.magpo_last_error.restype = ctypes.c_char_p

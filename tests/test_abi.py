@@ -79,3 +79,17 @@ def test_product_does_not_import_the_oracle():
     for f in root.rglob("*.py"):
         src = f.read_text()
         assert "import oracle" not in src and "from oracle" not in src, f
+
+
+def test_library_shares_torchs_hip_runtime_whatever_the_import_order(built):
+    """Loaded before anything imported torch (as build() does), the library must still bind to the HIP / HSA runtimes torch
+    bundles: a second copy of the runtimes in the process leaves the library without a device (build() then smoke() in one process)."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import sys; from magpo_amd._lib import lib; lib(); import torch\n"
+            "maps = {l.split()[-1] for l in open('/proc/self/maps') if l.split()[-1].startswith('/')}\n"
+            "print(len([p for p in maps if 'libamdhip64' in p]), len([p for p in maps if 'libhsa-runtime64' in p]))")
+    r = subprocess.run([sys.executable, "-s", "-c", code], capture_output=True, text=True, cwd=root, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stdout.split()[-2:] == ["1", "1"], r.stdout

@@ -153,6 +153,27 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     assert roof["bound"] in ("hbm", "mfma") and abs(roof["frac"] - roof["achieved"] / roof["peak"]) < 1e-3
 
 
+def test_bench_dumps_the_outputs_of_its_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR`: after the timed steps, the loss table, parameters, Adam moments and episode metrics of the last
+    timed update step land in DIR as float32 .npy files (finite, at most 64 MB in all), and --steps sets the number of timed steps."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--num-envs", "256", "--steps", "2", "--warmup", "0", "--no-cpu-baseline",
+                        "--no-variants", "--no-kernel-timing", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads(r.stdout.strip().splitlines()[-1])["steps"] == 2
+    files = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert {"losses", "guider_params", "actor_params", "guider_adam_mu", "actor_adam_nu", "metrics_episode_return"} <= set(files)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert files["losses"].shape == (4, 2, 9) and files["metrics_episode_return"].shape == (128, 256)
+    assert np.abs(files["guider_adam_nu"]).sum() > 0
+
+
 def test_lr_decay_uses_the_num_updates_check_total_timesteps_derives(tmp_path):
     """linear_scedule (mava/utils/training.py:37-43) reads config.system.num_updates when the learner is traced, i.e. AFTER
     check_total_timesteps rewrote it (rec_magpo.py:581 builds the optimiser before :717, but the closure holds the same config): with
