@@ -100,7 +100,8 @@ int magpo_coordsum_class_rows(int A, int maxval, int npos, int K, float* obs_tab
 
 /* ---- dense layers on fp32 MFMA (flax nn.Dense / retention projections) ----
  * act: 0 none, 1 relu, 2 gelu(tanh), 3 swish, 4 mask: Y = (M > 0) ? XW+b : 0 with the mask M passed in the Ypre argument (same stride as Y)
- * -- the ReLU backward fused into dX = dY W^T.  Ypre (act 0-3, nullable): receives the pre-activation. */
+ * -- the ReLU backward fused into dX = dY W^T, 5 tanh, 6 tanh backward: Y = (XW+b) (1 - M^2) with the forward's tanh output M in the Ypre
+ * argument (KIN in {64, 128, 192, 256, 384}; variant bits 0 / 1 are ignored).  Ypre (act 0-3 and 5, nullable): receives the pre-activation. */
 /* variant: 0 = fast path; A/B reference kernels with the same result up to fp32 summation order: linear bit 0 = wave-autonomous kernels
  * instead of the shared-tile ones, bit 1 = the same for KIN = 64 only, bit 2 = KIN 128 / 192 with at least 128 output columns (four-wave column blocks) on bf16 MFMA with both operands
  * split into three bf16 pieces (24 mantissa bits, six products, fp32 accumulate: fp32 accuracy at 6/16 of the fp32 MFMA time; ignored for other shapes); wgrad bit mask 1 = split kernel for every shape, 2 = generic whole-matrix
@@ -135,6 +136,14 @@ int magpo_embed_bwd(int mode, const float* z, int ldz, const float* d0, int ldd0
                     const float* d2, int ldd2, const float* s_ln, float* dz, int lddz, float* slab_sln,
                     float* slab_w, int nrows, const float* obs, int ldo, int F, const float* s_obs, const float* W,
                     float* slab_sobs, const int* idx, int idx_stride, long R, int E, magpo_stream_t stream);
+/* actor MLPTorso layer with LayerNorm (torsos.py:36-47): y = act(LayerNorm(z) + b) over rows of D floats, D in {64, 128, 192, 256};
+ * LayerNorm(use_scale=False): (z - mean) rstd, rstd = rsqrt(max(E[z^2] - E[z]^2, 0) + 1e-6); act 0 none, 1 relu, 5 tanh (magpo_linear's codes).
+ * fwd writes y, xhat = (z - mean) rstd and rstd [R]; bwd: g = dy act'(y), dz = rstd (g - mean(g) - xhat mean(g xhat)), slab_b
+ * [magpo_row_grid(R)][D] = per-workgroup column sums of g (the bias gradient, for magpo_reduce_slabs).  Strides multiples of 4. */
+int magpo_ln_act_fwd(const float* z, int ldz, const float* bias, float* y, int ldy, float* xhat, int ldxh, float* rstd, long R, int D,
+                     int act, magpo_stream_t stream);
+int magpo_ln_act_bwd(const float* dy, int lddy, const float* y, int ldy, const float* xhat, int ldxh, const float* rstd, float* dz,
+                     int lddz, float* slab_b, long R, int D, int act, magpo_stream_t stream);
 int magpo_small_relu_wgrad(const float* X, int ldx, int F, const float* Yact, const float* dY, float* slab_w, long R,
                            magpo_stream_t stream);
 int magpo_small_operand(int mode, const float* obs, int ldo, int F, const float* s_obs, const int* idx,

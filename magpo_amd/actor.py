@@ -1,7 +1,9 @@
 """Decentralised GRU actor (RecurrentActor, mava/networks/base.py:152-184) on the MI355X kernels.
 
-pre-torso Dense(F->128)+ReLU -> scanned GRU(128) with done-resets -> post-torso Dense(128->128)+ReLU
--> Dense(128->K) logits (masked categorical head, heads.py:26-63).  ``step`` pushes the carry during
+pre-torso MLPTorso (default Dense(F->128)+ReLU) -> scanned GRU(128) with done-resets -> post-torso MLPTorso (default
+Dense(128->128)+ReLU) -> Dense(D_post->K) logits (masked categorical head, heads.py:26-63).  The torsos follow
+``network.actor_network.{pre,post}_torso`` (magpo_amd/torso.py): 1-3 layers of width 64-256, relu / tanh, optional
+LayerNorm (magpo_ln_act_fwd / _bwd after the dense layer).  ``step`` pushes the carry during
 the rollout (rec_magpo.py:146-159) and serves the evaluator; ``seq_fwd`` / ``seq_bwd`` are the
 training forward and the hand-derived BPTT backward.
 """
@@ -17,6 +19,7 @@ import torch
 from ._lib import lib
 from .params import FlatParams, actor_layout, actor_named_views, init_actor
 from .sable import _Bufs
+from .torso import DEFAULT_TORSO, TorsoSpec, layer_name
 from .tuning import Tuning
 
 H = 128
@@ -24,7 +27,8 @@ H = 128
 
 class GruActor:
     def __init__(self, n_agents: int, action_dim: int, obs_dim: int, device, *, hidden: int = 128, wgrad_groups: int = 512,
-                 seed: Optional[int] = None, grads: Optional[torch.Tensor] = None, tuning: Optional[Tuning] = None, obs_ld: Optional[int] = None):
+                 seed: Optional[int] = None, grads: Optional[torch.Tensor] = None, tuning: Optional[Tuning] = None, obs_ld: Optional[int] = None,
+                 pre_torso: Optional[TorsoSpec] = None, post_torso: Optional[TorsoSpec] = None):
         self.tuning = tuning if tuning is not None else Tuning.from_env()   # per-call kernel knobs (tuning.py); the library keeps none
         if hidden != 128:
             raise NotImplementedError("gfx950 GRU kernels: hidden_state_dim = 128 only")
@@ -37,10 +41,18 @@ class GruActor:
             if self.wide or int(obs_ld) < obs_dim:
                 raise ValueError(f"obs_ld={obs_ld} with obs_dim={obs_dim}: a separate row stride is supported for narrow observations only")
             self.Fld = int(obs_ld)
+        self.pre_spec = pre_torso if pre_torso is not None else DEFAULT_TORSO
+        self.post_spec = post_torso if post_torso is not None else DEFAULT_TORSO
+        self.Dpre, self.Dpost = self.pre_spec.width, self.post_spec.width
+        # first pre-torso layer on narrow observations: the small-input kernels serve Dense(F->128)+ReLU without LayerNorm; any other first
+        # layer reads the observations as a zero-padded [R][64] operand (magpo_small_operand) through magpo_linear / magpo_wgrad
+        p0 = self.pre_spec
+        self.small_first = not self.wide and p0.layer_sizes[0] == 128 and p0.act(0) == 1 and not p0.use_layer_norm
+        self.KP = 128 if self.wide else 64    # columns of the first layer's (padded) operand
         self.dev = device
         self.L = lib()
         self.G = wgrad_groups
-        self.P = FlatParams(actor_layout(obs_dim, H, action_dim), device)
+        self.P = FlatParams(actor_layout(obs_dim, H, action_dim, self.pre_spec, self.post_spec), device)
         self.grads = torch.zeros_like(self.P.flat) if grads is None else grads
         assert self.grads.numel() == self.P.numel
         self.v = self.P.views()
@@ -56,7 +68,12 @@ class GruActor:
         self.b = _Bufs(device)
         self.wgrad_stream = torch.cuda.Stream(device=device) if torch.device(device).type == "cuda" else None
         self.overlap_wgrad = False  # opt-in (bench.py --overlap): ~0.5 %, but per-kernel timings then include contention
-        self.wg_ws = torch.empty(self.L.call("magpo_wgrad_workspace_floats", H, 3 * H, self.G), device=device)
+        shapes = [(H, 3 * H), (self.Dpre, 3 * H), (self.Dpost, self.K)]   # every (KIN, NOUT) of a weight gradient
+        for spec, din in ((self.pre_spec, self.KP), (self.post_spec, H)):
+            for d in spec.layer_sizes:
+                shapes.append((din, d))
+                din = d
+        self.wg_ws = torch.empty(max(self.L.call("magpo_wgrad_workspace_floats", k, n, self.G) for k, n in shapes), device=device)
         self.refresh()
 
     def _st(self):
@@ -87,17 +104,21 @@ class GruActor:
 
     def refresh(self):
         v = self.v
-        if self.wide:   # W_pre [F, 128] as [128][128] with zero columns beyond F
+        if not self.small_first:   # W_pre [F, D0] as [D0][KP] with zero columns beyond F
             if "pre" not in self.wt:
-                self.wt["pre"] = torch.zeros(H, 128, device=self.dev)
+                self.wt["pre"] = torch.zeros(self.pre_spec.layer_sizes[0], self.KP, device=self.dev)
             self.wt["pre"][:, :self.F].copy_(v["pre.kernel"].t())
-        self._tp("wi", v["gru.wi"]); self._tp("wh", v["gru.wh"]); self._tp("post", v["post.kernel"])
-        ht = self._tp("head", v["head.kernel"], 64)      # [64][128]
-        self._tp("head_nat_pad", ht, H)                   # [128][64]
+        self._tp("wi", v["gru.wi"]); self._tp("wh", v["gru.wh"])
+        for prefix, spec in (("pre", self.pre_spec), ("post", self.post_spec)):
+            for i in range(1 if prefix == "pre" else 0, len(spec.layer_sizes)):
+                n = layer_name(prefix, i)
+                self._tp(n, v[n + ".kernel"])
+        ht = self._tp("head", v["head.kernel"], 64)      # [64][D_post]
+        self._tp("head_nat_pad", ht, self.Dpost)          # [D_post][64]
         # W_i with its gate columns in the order of the backward scan's gradient matrix (n | r | z), see seq_bwd
         if "wi_nrz" not in self.wt:
-            self.wt["wi_nrz"] = torch.empty(H, 3 * H, device=self.dev)
-        self._cols_nrz(v["gru.wi"], self.wt["wi_nrz"], H, inverse=True)
+            self.wt["wi_nrz"] = torch.empty(self.Dpre, 3 * H, device=self.dev)
+        self._cols_nrz(v["gru.wi"], self.wt["wi_nrz"], self.Dpre, inverse=True)
 
     def _cols_nrz(self, src, dst, rows, inverse=False):
         """[rows, 3H] matrices, gate column blocks (n | r | z) -> (r | z | n) (inverse: the other way), on the current stream."""
@@ -112,12 +133,84 @@ class GruActor:
     def lin(self, X, ldx, Wt, bias, Y, ldy, R, KIN, NOUT, act=0, Ypre=None):
         self.L.call("magpo_linear", X, ldx, Wt, bias, Y, ldy, Ypre, R, KIN, NOUT, act, self.tuning.actor_linear_variant, self._st())
 
-    def pre_torso(self, obs, emb, R):
-        """emb = relu(obs W_pre + b) (MLPTorso, torsos.py:36-47) for R observation rows (stride self.Fld)."""
-        if self.wide:
-            self.lin(obs, 128, self.wt["pre"], self.v["pre.bias"], emb, H, R, 128, H, act=1)
-        else:
-            self.L.call("magpo_small_linear", obs, self.Fld, self.F, self.v["pre.kernel"], self.v["pre.bias"], emb, H, H, R, 1, self._st())
+    def _torso_fwd(self, prefix, spec, X, ldx, R, ctx):
+        """One MLPTorso (torsos.py:36-47) on R rows of X (stride ldx; the pre-torso's X are observation rows of F features).  Buffers are
+        named by ``ctx`` so that the rollout, the carry and the training forward keep their own.  Returns one record per layer:
+        (input, input stride, KIN, output y [R, width], (xhat, rstd) of the LayerNorm or None)."""
+        L, st, v, b = self.L, self._st(), self.v, self.b
+        recs = []
+        kin = ldx if prefix == "post" else None
+        for i, d in enumerate(spec.layer_sizes):
+            n = layer_name(prefix, i)
+            y = b.get(f"{ctx}{n}.y", (R, d))
+            Wt = self.wt.get(n)
+            if prefix == "pre" and i == 0:
+                if self.small_first:
+                    L.call("magpo_small_linear", X, ldx, self.F, v["pre.kernel"], v["pre.bias"], y, d, d, R, 1, st)
+                    recs.append((X, ldx, None, y, None))
+                    X, ldx, kin = y, d, d
+                    continue
+                if not self.wide:   # observation rows as a zero-padded [R][64] operand
+                    xp = b.get(f"{ctx}pre.xp", (R, 64))
+                    L.call("magpo_small_operand", 2, X, ldx, self.F, None, None, 0, xp, R, st)
+                    X, ldx = xp, 64
+                kin, Wt = self.KP, self.wt["pre"]
+            if spec.use_layer_norm:
+                z = b.get(f"{ctx}{n}.z", (R, d)); xh = b.get(f"{ctx}{n}.xh", (R, d)); rs = b.get(f"{ctx}{n}.rs", (R,))
+                self.lin(X, ldx, Wt, v[n + ".bias"], z, d, R, kin, d)
+                L.call("magpo_ln_act_fwd", z, d, v[n + ".ln.bias"], y, d, xh, d, rs, R, d, spec.act(i), st)
+                recs.append((X, ldx, kin, y, (xh, rs)))
+            else:
+                self.lin(X, ldx, Wt, v[n + ".bias"], y, d, R, kin, d, act=spec.act(i))
+                recs.append((X, ldx, kin, y, None))
+            X, ldx, kin = y, d, d
+        return recs
+
+    def pre_torso(self, obs, obs_ld, R, ctx):
+        """Pre-torso on R observation rows (stride obs_ld) -> its layer records; the output (GRU input) is recs[-1][3], [R, D_pre]."""
+        return self._torso_fwd("pre", self.pre_spec, obs, obs_ld, R, ctx)
+
+    def post_torso_logits(self, hs, R, ctx, logits):
+        """Post-torso on the hidden states hs [R,128] and the logit head into logits [R,64] (K valid columns)."""
+        recs = self._torso_fwd("post", self.post_spec, hs, H, R, ctx)
+        self.lin(recs[-1][3], self.Dpost, self.wt["head"], self.v["head.bias"], logits, 64, R, self.Dpost, self.K)
+        return recs
+
+    def _torso_bwd(self, prefix, spec, recs, dy):
+        """Backward through one torso.  ``dy`` = gradient at the last layer's output, already multiplied by that layer's activation
+        derivative when the layer has no LayerNorm (the GEMM that produced it fused the mask: act 4 / 6).  Fills the layers' parameter
+        gradients; returns the gradient at layer 0's pre-activation (the small first layer: at its output, unmasked)."""
+        L, st, gv, v, b = self.L, self._st(), self.gv, self.v, self.b
+        R = dy.shape[0]
+        for i in range(len(spec.layer_sizes) - 1, -1, -1):
+            n = layer_name(prefix, i)
+            d = spec.layer_sizes[i]
+            X, ldx, kin, y, ln = recs[i]
+            if prefix == "pre" and i == 0 and self.small_first:
+                return dy
+            if ln is not None:   # LayerNorm + activation backward on the rows; the LayerNorm bias gradient from per-workgroup slabs
+                dz = b.get(f"g_{prefix}{i}.dz", (R, d))
+                grid = L.call("magpo_row_grid", R)
+                slab = b.get(f"g_{prefix}{i}.slab", (grid, d))
+                L.call("magpo_ln_act_bwd", dy, d, y, d, ln[0], d, ln[1], dz, d, slab, R, d, spec.act(i), st)
+                L.call("magpo_reduce_slabs", slab, gv[n + ".ln.bias"], grid, d, d, 1.0, 0, st)
+            else:
+                dz = dy
+            krows = self.F if (prefix == "pre" and i == 0) else None
+            self.wgrad(X, ldx, dz, d, R, kin, d, gv[n + ".kernel"], gv[n + ".bias"], krows=krows)
+            if i == 0:
+                return dz
+            dy = b.get(f"g_{prefix}{i - 1}.dy", (R, spec.layer_sizes[i - 1]))
+            self._dx(dz, d, v[n + ".kernel"], d, spec.layer_sizes[i - 1], R, dy, spec, i - 1, recs[i - 1])
+        return dy
+
+    def _dx(self, dsrc, ldsrc, W_nat, KIN, NOUT, R, dst, spec, j, rec):
+        """dst = dsrc W^T (W in its natural [NOUT, KIN] layout), times the activation derivative of layer j of ``spec`` when that
+        layer has no LayerNorm (fused epilogue: act 4 ReLU mask / act 6 tanh, its output in the Ypre slot)."""
+        act, M = 0, None
+        if rec[4] is None and spec.act(j):
+            act, M = (4 if spec.act(j) == 1 else 6), rec[3]
+        self.lin(dsrc, ldsrc, W_nat, None, dst, NOUT, R, KIN, NOUT, act=act, Ypre=M)
 
     def _groups(self, R):
         """Row slabs of a split weight gradient: no more than one per 256 rows (small minibatches: fewer partials to reduce)."""
@@ -135,14 +228,15 @@ class GruActor:
 
     def _wgrad_nrz(self, emb, dg, R, gw, dW, db):
         """dW_i, db_i from dg's columns 0..3H (gate blocks n | r | z) into W_i's order, on the weight-gradient stream."""
+        D = self.Dpre
         side = self.wgrad_stream if self.overlap_wgrad else None
         if side is not None:
             side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
             st = self._st()
-            self.L.call("magpo_wgrad", emb, H, dg, 4 * H, R, H, H, 3 * H, gw[:H], gw[H], self.wg_ws, self._groups(R), 1.0, 0, self.tuning.wgrad_variant, st)
-            self._cols_nrz(gw[:H], dW, H)
-            self._cols_nrz(gw[H:], db.view(1, 3 * H), 1)
+            self.L.call("magpo_wgrad", emb, D, dg, 4 * H, R, D, D, 3 * H, gw[:D], gw[D], self.wg_ws, self._groups(R), 1.0, 0, self.tuning.wgrad_variant, st)
+            self._cols_nrz(gw[:D], dW, D)
+            self._cols_nrz(gw[D:], db.view(1, 3 * H), 1)
 
     # one step for N envs: returns new hidden [N*A,128]; logits [N*A,64] if want_logits
     def step(self, obs, h_in, reset_env, h_out, want_logits: bool = False):
@@ -150,15 +244,14 @@ class GruActor:
         L, st, A, F, v, b = self.L, self._st(), self.A, self.F, self.v, self.b
         N = obs.shape[0]
         R = N * A
-        emb = b.get("s_emb", (R, H)); xi = b.get("s_xi", (R, 3 * H))
-        self.pre_torso(obs, emb, R)
-        self.lin(emb, H, self.wt["wi"], v["gru.bi"], xi, 3 * H, R, H, 3 * H)
+        xi = b.get("s_xi", (R, 3 * H))
+        emb = self.pre_torso(obs, self.Fld, R, "s_")[-1][3]
+        self.lin(emb, self.Dpre, self.wt["wi"], v["gru.bi"], xi, 3 * H, R, self.Dpre, 3 * H)
         L.call("magpo_gru_scan_fwd", xi, self.wt["wh"], v["gru.hn.bias"], h_in, None, reset_env, h_out, None, None, N, 1, A, None, 0, self.tuning.gru_block_rows, st)
         if not want_logits:
             return None
-        y = b.get("s_y", (R, H)); logits = b.get("s_logits", (R, 64), zero=True)
-        self.lin(h_out, H, self.wt["post"], v["post.bias"], y, H, R, H, H, act=1)
-        self.lin(y, H, self.wt["head"], v["head.bias"], logits, 64, R, H, self.K)
+        logits = b.get("s_logits", (R, 64), zero=True)
+        self.post_torso_logits(h_out, R, "s_", logits)
         return logits
 
     def carry(self, obs_tm, h_in, reset_tm, h_out, classes=None, tag=""):
@@ -173,20 +266,20 @@ class GruActor:
             _, xi_tab = self.input_table(classes[0], "r" + tag)
             L.call("magpo_gru_carry", xi_tab, self.wt["wh"], v["gru.hn.bias"], h_in, reset_tm, h_out, N, T, A, classes[1], self.tuning.gru_block_rows, st)
             return
-        emb = b.get("c_emb", (R, H)); xi = b.get("c_xi", (R, 3 * H))
-        self.pre_torso(obs_tm, emb, R)
-        self.lin(emb, H, self.wt["wi"], v["gru.bi"], xi, 3 * H, R, H, 3 * H)
+        xi = b.get("c_xi", (R, 3 * H))
+        emb = self.pre_torso(obs_tm, self.Fld, R, "c_")[-1][3]
+        self.lin(emb, self.Dpre, self.wt["wi"], v["gru.bi"], xi, 3 * H, R, self.Dpre, 3 * H)
         L.call("magpo_gru_carry", xi, self.wt["wh"], v["gru.hn.bias"], h_in, reset_tm, h_out, N, T, A, None, self.tuning.gru_block_rows, st)
 
     def input_table(self, obs_tab: torch.Tensor, tag: str = ""):
         """xi of every distinct observation row: pre-torso + GRU input projection on obs_tab [C,F] -> [C,384] (the rows of a
-        minibatch then take their xi by class index; see csrc/classtab.hip)."""
-        L, st, F, v, b = self.L, self._st(), self.F, self.v, self.b
+        minibatch then take their xi by class index; see csrc/classtab.hip).  Returns (pre-torso layer records, xi table)."""
+        v, b = self.v, self.b
         C = obs_tab.shape[0]
-        emb_tab = b.get("c_embtab" + tag, (C, H)); xi_tab = b.get("c_xitab" + tag, (C, 3 * H))
-        L.call("magpo_small_linear", obs_tab, F, F, v["pre.kernel"], v["pre.bias"], emb_tab, H, H, C, 1, st)
-        self.lin(emb_tab, H, self.wt["wi"], v["gru.bi"], xi_tab, 3 * H, C, H, 3 * H)
-        return emb_tab, xi_tab
+        xi_tab = b.get("c_xitab" + tag, (C, 3 * H))
+        recs = self.pre_torso(obs_tab, self.F, C, "c_tab" + tag + "_")
+        self.lin(recs[-1][3], self.Dpre, self.wt["wi"], v["gru.bi"], xi_tab, 3 * H, C, self.Dpre, 3 * H)
+        return recs, xi_tab
 
     def seq_fwd(self, obs, dones, h0, h0_idx, nseq: int, T: int, classes=None):
         """obs [R,F] rows (seq, t, agent); dones [nseq,T] u8 resets; h0 [*,128] gathered through h0_idx [nseq*A].
@@ -196,20 +289,19 @@ class GruActor:
         L, st, A, F, v, b = self.L, self._st(), self.A, self.F, self.v, self.b
         R = nseq * T * A
         hs = b.get("t_hs", (R, H))
-        gates = b.get("t_gates", (R, 4 * H)); hprev = b.get("t_hprev", (R, H)); y = b.get("t_y", (R, H))
+        gates = b.get("t_gates", (R, 4 * H)); hprev = b.get("t_hprev", (R, H))
         logits = b.get("t_logits", (R, 64), zero=True)
-        self._saved = dict(obs=obs, dones=dones, nseq=nseq, T=T, R=R, classes=classes)
         if classes is not None:   # the scan reads xi rows straight from the (L2-resident) class table
-            _, xi = self.input_table(classes[0])
+            pre, xi = self.input_table(classes[0])
             xi_cls = classes[1]
         else:
-            emb = b.get("t_emb", (R, H)); xi = b.get("t_xi", (R, 3 * H))
+            xi = b.get("t_xi", (R, 3 * H))
             xi_cls = None
-            self.pre_torso(obs, emb, R)
-            self.lin(emb, H, self.wt["wi"], v["gru.bi"], xi, 3 * H, R, H, 3 * H)
+            pre = self.pre_torso(obs, self.Fld, R, "t_")
+            self.lin(pre[-1][3], self.Dpre, self.wt["wi"], v["gru.bi"], xi, 3 * H, R, self.Dpre, 3 * H)
         L.call("magpo_gru_scan_fwd", xi, self.wt["wh"], v["gru.hn.bias"], h0, h0_idx, dones, hs, gates, hprev, nseq, T, A, xi_cls, self.tuning.gru_split_bf16, self.tuning.gru_block_rows, st)
-        self.lin(hs, H, self.wt["post"], v["post.bias"], y, H, R, H, H, act=1)
-        self.lin(y, H, self.wt["head"], v["head.bias"], logits, 64, R, H, self.K)
+        post = self.post_torso_logits(hs, R, "t_", logits)
+        self._saved = dict(obs=obs, dones=dones, nseq=nseq, T=T, R=R, classes=classes, pre=pre, post=post)
         return logits
 
     def seq_bwd(self, dlogits):
@@ -217,22 +309,22 @@ class GruActor:
         L, st, A, F, K, v, gv, b = self.L, self._st(), self.A, self.F, self.K, self.v, self.gv, self.b
         sv = self._saved
         R, nseq, T, obs, dones = sv["R"], sv["nseq"], sv["T"], sv["obs"], sv["dones"]
-        t = lambda n: b.t["t_" + n]
-        self.wgrad(t("y"), H, dlogits, 64, R, H, K, gv["head.kernel"], gv["head.bias"])
-        dy = b.get("g_dy", (R, H))
-        # dy = (dlogits @ W_head^T) masked by the forward ReLU (fused epilogue: act 4 takes the mask in the Ypre slot)
-        self.lin(dlogits, 64, self.wt["head_nat_pad"], None, dy, H, R, 64, H, act=4, Ypre=t("y"))
-        self.wgrad(t("hs"), H, dy, H, R, H, H, gv["post.kernel"], gv["post.bias"])
+        post, pre, Dq, Dp = sv["post"], sv["pre"], self.Dpost, self.Dpre
+        self.wgrad(post[-1][3], Dq, dlogits, 64, R, Dq, K, gv["head.kernel"], gv["head.bias"])
+        dy = b.get("g_post_dy", (R, Dq))
+        # dy = dlogits @ W_head^T, masked by the last post-torso layer's activation (fused epilogue: act 4 / 6 take the mask in the Ypre slot)
+        self._dx(dlogits, 64, self.wt["head_nat_pad"], 64, Dq, R, dy, self.post_spec, len(post) - 1, post[-1])
+        dz0 = self._torso_bwd("post", self.post_spec, post, dy)
         dhs = b.get("g_dhs", (R, H))
-        self.lin(dy, H, v["post.kernel"], None, dhs, H, R, H, H)
+        self.lin(dz0, self.post_spec.layer_sizes[0], v["post.kernel"], None, dhs, H, R, self.post_spec.layer_sizes[0], H)
         # one gradient matrix for both projections (include/magpo.h): dg = (dn_in | dr | dz | dn_hid); the hidden side is its columns
         # H..4H in W_h's own gate order, the input side its columns 0..3H in the order (n | r | z)
         dg = b.get("g_dg", (R, 4 * H))
         nblk = (nseq * A + 63) // 64
         slab = b.get("g_slab", (nblk, H))
-        L.call("magpo_gru_scan_bwd", t("gates"), t("hprev"), dones, dhs, v["gru.wh"], dg, slab, nseq, T, A, self.tuning.gru_split_bf16, self.tuning.gru_block_rows, st)
+        L.call("magpo_gru_scan_bwd", b.t["t_gates"], b.t["t_hprev"], dones, dhs, v["gru.wh"], dg, slab, nseq, T, A, self.tuning.gru_split_bf16, self.tuning.gru_block_rows, st)
         L.call("magpo_reduce_slabs", slab, gv["gru.hn.bias"], nblk, H, H, 1.0, 0, st)
-        self.wgrad(t("hprev"), H, dg[:, H:], 4 * H, R, H, 3 * H, gv["gru.wh"])
+        self.wgrad(b.t["t_hprev"], H, dg[:, H:], 4 * H, R, H, 3 * H, gv["gru.wh"])
         if sv["classes"] is not None:
             # input side on the class table: S[c] = sum of the rows of class c, gate blocks back into W_i's order on the C rows, then the
             # layers' backward on C rows
@@ -242,29 +334,30 @@ class GruActor:
             s_nrz = b.get("g_dxic_nrz", (C, 3 * H)); dxi = b.get("g_dxic", (C, 3 * H))
             L.call("magpo_class_sum", dg, 4 * H, order, offsets, C, 3 * H, part, s_nrz, st)
             self._cols_nrz(s_nrz, dxi, C)
-            emb, R = b.t["c_embtab"], C
-            self.wgrad(emb, H, dxi, 3 * H, R, H, 3 * H, gv["gru.wi"], gv["gru.bi"])
+            emb, R = pre[-1][3], C
+            self.wgrad(emb, Dp, dxi, 3 * H, R, Dp, 3 * H, gv["gru.wi"], gv["gru.bi"])
             ldx, wi_t = 3 * H, v["gru.wi"]
         else:
-            # per token row: weight gradient with its gate blocks in dg's order, put back into W_i's order on the [H, 3H] result; the dX
+            # per token row: weight gradient with its gate blocks in dg's order, put back into W_i's order on the [D_pre, 3H] result; the dX
             # GEMM contracts over the gates in dg's order against the equally permuted copy of W_i
-            emb = t("emb")
-            gw = b.get("g_gwi_nrz", (H + 1, 3 * H))
+            emb = pre[-1][3]
+            gw = b.get("g_gwi_nrz", (Dp + 1, 3 * H))
             self._wgrad_nrz(emb, dg, R, gw, gv["gru.wi"], gv["gru.bi"])
             dxi, ldx, wi_t = dg, 4 * H, self.wt["wi_nrz"]
-        demb = b.get("g_demb", (R, H))
-        if self.wide:   # ReLU backward fused into the dX GEMM (act 4 takes the mask), then dW_pre = obs^T demb on the dense kernel
-            self.lin(dxi, ldx, wi_t, None, demb, H, R, 3 * H, H, act=4, Ypre=emb)
-            self.wgrad(obs, 128, demb, H, R, 128, H, gv["pre.kernel"], gv["pre.bias"], krows=F)
-            if self.overlap_wgrad and self.wgrad_stream is not None:
-                torch.cuda.current_stream().wait_stream(self.wgrad_stream)
-            return
-        self.lin(dxi, ldx, wi_t, None, demb, H, R, 3 * H, H)
-        grid = L.call("magpo_row_grid", R)
-        sw = b.get("g_slabw", (grid, 33 * H))
-        L.call("magpo_small_relu_wgrad", obs, self.Fld, F, emb, demb, sw, R, st)
-        L.call("magpo_reduce_slabs", sw, gv["pre.kernel"], grid, F * H, 33 * H, 1.0, 0, st)
-        L.call("magpo_reduce_slabs", sw[:, 32 * H:], gv["pre.bias"], grid, H, 33 * H, 1.0, 0, st)
+        demb = b.get("g_demb", (R, Dp))
+        # dX of the GRU input projection, masked by the last pre-torso layer's activation (the small first layer applies its ReLU mask itself)
+        if len(pre) == 1 and self.small_first:
+            self.lin(dxi, ldx, wi_t, None, demb, Dp, R, 3 * H, Dp)
+        else:
+            self._dx(dxi, ldx, wi_t, 3 * H, Dp, R, demb, self.pre_spec, len(pre) - 1, pre[-1])
+        d0 = self._torso_bwd("pre", self.pre_spec, pre, demb)
+        if self.small_first:   # Dense(F->128)+ReLU weight gradient on the raw observation rows
+            emb0 = pre[0][3]
+            grid = L.call("magpo_row_grid", R)
+            sw = b.get("g_slabw", (grid, 33 * H))
+            L.call("magpo_small_relu_wgrad", obs, self.Fld, F, emb0, d0, sw, R, st)
+            L.call("magpo_reduce_slabs", sw, gv["pre.kernel"], grid, F * H, 33 * H, 1.0, 0, st)
+            L.call("magpo_reduce_slabs", sw[:, 32 * H:], gv["pre.bias"], grid, H, 33 * H, 1.0, 0, st)
         if self.overlap_wgrad and self.wgrad_stream is not None:
             torch.cuda.current_stream().wait_stream(self.wgrad_stream)
 

@@ -15,7 +15,8 @@
 
 namespace magpo {
 
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_SWISH = 3, ACT_MASKPOS = 4 };   // MASKPOS: y = aux > 0 ? y : 0 (ReLU backward fused into dX = dY W^T)
+// MASKPOS: y = aux > 0 ? y : 0 (ReLU backward fused into dX = dY W^T); TANHBWD: y *= 1 - aux^2 (tanh backward, aux = the forward's output)
+enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_SWISH = 3, ACT_MASKPOS = 4, ACT_TANH = 5, ACT_TANHBWD = 6 };
 
 template <int KIN>
 __global__ __launch_bounds__(256) void k_linear(const float* __restrict__ X, int ldx,
@@ -74,6 +75,7 @@ __global__ __launch_bounds__(256) void k_linear(const float* __restrict__ X, int
           if (act == ACT_RELU) v = fmaxf(v, 0.f);
           else if (act == ACT_GELU) v = gelu_tanh(v);
           else if (act == ACT_SWISH) v = swishf_(v);
+          else if (act == ACT_TANH) v = tanhf(v);
           Y[gr * (long)ldy + n] = v;
         }
       }
@@ -158,6 +160,7 @@ __global__ __launch_bounds__(256) void k_linear_w(const float* __restrict__ X, i
               if (act == ACT_RELU) v = fmaxf(v, 0.f);
               else if (act == ACT_GELU) v = gelu_tanh(v);
               else if (act == ACT_SWISH) v = swishf_(v);
+              else if (act == ACT_TANH) v = tanhf(v);
               Y[gr * (long)ldy + n] = v;
             }
           }
@@ -394,6 +397,7 @@ __global__ __launch_bounds__(256) void k_linear_wk(const float* __restrict__ X, 
           if (act == ACT_RELU) v = fmaxf(v, 0.f);
           else if (act == ACT_GELU) v = gelu_tanh(v);
           else if (act == ACT_SWISH) v = swishf_(v);
+          else if (act == ACT_TANH) v = tanhf(v);
           Y[gr * (long)ldy + n] = v;
         }
       }
@@ -601,7 +605,9 @@ __global__ __launch_bounds__(64 * NW) void k_linear_lds(const float* __restrict_
             if (act == ACT_RELU) v = fmaxf(v, 0.f);
             else if (act == ACT_GELU) v = gelu_tanh(v);
             else if (act == ACT_SWISH) v = swishf_(v);
+            else if (act == ACT_TANH) v = tanhf(v);
             else if (act == ACT_MASKPOS) v = aux[gr * (long)ldy + n] > 0.f ? v : 0.f;
+            else if (act == ACT_TANHBWD) { const float t = aux[gr * (long)ldy + n]; v *= 1.f - t * t; }
             Y[gr * (long)ldy + n] = v;
           }
         }
@@ -1237,10 +1243,15 @@ extern "C" int magpo_linear(const float* X, int ldx, const float* Wt, const floa
   if (variant < 0 || variant > 7) { set_error("magpo_linear: variant must be in [0, 7]"); return MAGPO_EINVAL; }
   const bool lds64 = !(variant & 2);
   const float* aux = nullptr;
-  if (act == ACT_MASKPOS) {   // the Ypre argument carries the mask INPUT (same shape / stride as Y), nothing else is written
-    if (!Ypre) { set_error("magpo_linear: act 4 (mask) needs the mask tensor in the Ypre argument"); return MAGPO_EINVAL; }
+  if (act < ACT_NONE || act > ACT_TANHBWD) { set_error("magpo_linear: act must be in [0, 6]"); return MAGPO_EINVAL; }
+  if (act == ACT_MASKPOS || act == ACT_TANHBWD) {   // the Ypre argument carries the mask INPUT (same shape / stride as Y), nothing else is written
+    if (!Ypre) { set_error("magpo_linear: act 4 / 6 (backward masks) need the mask tensor in the Ypre argument"); return MAGPO_EINVAL; }
     aux = Ypre;
     Ypre = nullptr;
+  }
+  if (act == ACT_TANHBWD) {   // only the shared-tile kernels read the mask
+    if (KIN != 64 && KIN != 128 && KIN != 192 && KIN != 256 && KIN != 384) { set_error("magpo_linear: act 6 needs KIN in {64, 128, 192, 256, 384}"); return MAGPO_EINVAL; }
+    variant &= 4;
   }
   if ((KIN == 128 || KIN == 192 || KIN == 256 || KIN == 384 || (KIN == 64 && lds64)) && !Ypre) {
     // persistent waves: one wave per (walker, 32-column group); blocks of 4 / 2 / 1 waves so that every wave slot of

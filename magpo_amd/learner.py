@@ -277,12 +277,13 @@ class MagpoLearner:
     def __init__(self, env_cfg, num_envs: int, sys: SystemConfig, device, *, net_seed: Optional[int] = 0,
                  decay_scaling_factor: float = 0.8, use_pe: bool = True, wgrad_groups: int = 512, num_groups: int = 1,
                  n_block: int = 1, n_head: int = 1, embed_dim: int = 64, tuning=None, guider: Optional[SableGuider] = None,
-                 actor: Optional[GruActor] = None, optims=None, apply_fns=None, update_fns=None):
+                 actor: Optional[GruActor] = None, optims=None, apply_fns=None, update_fns=None, actor_torso=(None, None)):
         """``guider`` / ``actor`` / ``optims`` = (guider ClipAdam, actor ClipAdam): networks and optimisers built by the caller
         (rec_magpo.learner_setup hands them to get_learner_fn as its apply / update functions); by default the learner builds its own.
         ``apply_fns`` = (sable_action_select_fn, sable_apply_fn, actor_apply_fn), ``update_fns`` = (sable_update_fn, actor_update_fn)
         (rec_magpo.py:99-100): the callables the loop CALLS for acting, the two training forwards and the two optimiser steps --
-        by default the bound methods of the objects above; get_learner_fn passes on what it was given (thin adaptors included)."""
+        by default the bound methods of the objects above; get_learner_fn passes on what it was given (thin adaptors included).
+        ``actor_torso`` = (pre, post) TorsoSpecs of the actor the learner builds itself (None: the default [128] relu torso)."""
         from .tuning import Tuning
         self.tuning = tuning if tuning is not None else (guider.tuning if guider is not None else Tuning.from_env())   # ONE object shared by both networks (tuning.py)
         self.env_cfg, self.N, self.sys, self.dev = env_cfg, num_envs, sys, device
@@ -300,7 +301,7 @@ class MagpoLearner:
             n_block, n_head, embed_dim = guider.nb, guider.nh, guider.EL
         self.nb, self.nh = int(n_block), int(n_head)
         gn = FlatParams(guider_layout(int(embed_dim), F, K, self.nb, self.nh), "cpu").numel
-        an = FlatParams(actor_layout(F, 128, K), "cpu").numel
+        an = actor.P.numel if actor is not None else FlatParams(actor_layout(F, 128, K, *actor_torso), "cpu").numel
         self.grad_all = torch.zeros(gn + an + 16, dtype=torch.float32, device=device)
         self.grad_acc = torch.zeros_like(self.grad_all) if num_groups > 1 else None
         self.grad_mu = torch.zeros_like(self.grad_all) if sys.micro_batches > 1 else None
@@ -312,7 +313,8 @@ class MagpoLearner:
             guider.bind_grads(self.grad_all[:gn])
         if actor is None:
             actor = GruActor(A, K, F, device, wgrad_groups=wgrad_groups, seed=None if net_seed is None else net_seed + 1,
-                             grads=self.grad_all[gn:gn + an], tuning=self.tuning, obs_ld=self.Fld)
+                             grads=self.grad_all[gn:gn + an], tuning=self.tuning, obs_ld=self.Fld, pre_torso=actor_torso[0],
+                             post_torso=actor_torso[1])
         else:
             actor.bind_grads(self.grad_all[gn:gn + an])
         if guider.F != F or actor.F != F or guider.Fld != self.Fld or actor.Fld != self.Fld:

@@ -205,18 +205,30 @@ class WidthEmbedding:
         return x.repeat_interleave(self.m, dim=-1).contiguous()
 
 
-def actor_layout(F: int, H: int, K: int) -> "OrderedDict[str, Tuple[int, ...]]":
+def actor_layout(F: int, H: int, K: int, pre=None, post=None) -> "OrderedDict[str, Tuple[int, ...]]":
+    """Actor parameters for torso specs ``pre`` / ``post`` (magpo_amd.torso.TorsoSpec, default [128] relu): Dense layer i of a torso is
+    ``pre`` / ``pre1`` / ``pre2`` (``.kernel`` [in, out], ``.bias``), its LayerNorm bias ``<layer>.ln.bias``."""
+    from .torso import DEFAULT_TORSO, layer_name
     assert H == 128, "the gfx950 GRU kernels are specialised for hidden_state_dim = 128"
     s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
-    s["pre.kernel"] = (F, H)
-    s["pre.bias"] = (H,)
-    s["gru.wi"] = (H, 3 * H)     # [ir | iz | in] kernels
+
+    def torso(prefix, spec, din):
+        for i, d in enumerate(spec.layer_sizes):
+            n = layer_name(prefix, i)
+            s[n + ".kernel"] = (din, d)
+            s[n + ".bias"] = (d,)
+            if spec.use_layer_norm:
+                s[n + ".ln.bias"] = (d,)
+            din = d
+        return din
+
+    d_pre = torso("pre", pre or DEFAULT_TORSO, F)
+    s["gru.wi"] = (d_pre, 3 * H)     # [ir | iz | in] kernels
     s["gru.bi"] = (3 * H,)
     s["gru.wh"] = (H, 3 * H)     # [hr | hz | hn] kernels
     s["gru.hn.bias"] = (H,)
-    s["post.kernel"] = (H, H)
-    s["post.bias"] = (H,)
-    s["head.kernel"] = (H, K)
+    d_post = torso("post", post or DEFAULT_TORSO, H)
+    s["head.kernel"] = (d_post, K)
     s["head.bias"] = (K,)
     return s
 
@@ -388,7 +400,10 @@ def init_guider_from_key(named: Dict[str, torch.Tensor], net_key: np.ndarray, E:
 
 
 def init_actor_from_key(named: Dict[str, torch.Tensor], actor_net_key: np.ndarray) -> None:
-    """The RecurrentActor parameters flax creates from ``actor_net_key`` (oracle/networks.py:init_actor_params_from_key)."""
+    """The RecurrentActor parameters flax creates from ``actor_net_key`` (oracle/networks.py:init_actor_params_from_key), for any torso
+    layout of actor_layout: MLPTorso's compact body names its layers Dense_0, LayerNorm_0, Dense_1, ... (only the Dense kernels are
+    random: LayerNorm(use_scale=False) has a zero bias), the GRU input kernels are lecun-normal over their fan-in D_pre."""
+    from .torso import layer_name
     s2 = math.sqrt(2.0)
     key = lambda path, c: _param_key(actor_net_key, path, c)
     with torch.no_grad():
@@ -396,14 +411,17 @@ def init_actor_from_key(named: Dict[str, torch.Tensor], actor_net_key: np.ndarra
             named[name].copy_(torch.from_numpy(np.ascontiguousarray(arr)).reshape(named[name].shape))
         for v in named.values():
             v.zero_()
-        F, H = named["pre.kernel"].shape
+        for prefix, scope in (("pre", "pre_torso"), ("post", "post_torso")):
+            i = 0
+            while layer_name(prefix, i) + ".kernel" in named:
+                put(layer_name(prefix, i) + ".kernel", _orth(key((scope, f"Dense_{i}"), 1), tuple(named[layer_name(prefix, i) + ".kernel"].shape), s2))
+                i += 1
+        D, H = named["gru.ir.kernel"].shape
         K = named["head.kernel"].shape[1]
-        put("pre.kernel", _orth(key(("pre_torso", "Dense_0"), 1), (F, H), s2))
         cell = ("ScannedRNN_0", "GRUCell_0")
-        std = np.float32(np.sqrt(np.float32(1.0) / np.float32(H))) / np.float32(0.87962566103423978)
+        std = np.float32(np.sqrt(np.float32(1.0) / np.float32(D))) / np.float32(0.87962566103423978)
         for g in ("ir", "iz", "in"):
-            put(f"gru.{g}.kernel", _trunc_normal(key(cell + (g,), 1), (H, H)) * std)
+            put(f"gru.{g}.kernel", _trunc_normal(key(cell + (g,), 1), (D, H)) * std)
         for g in ("hr", "hz", "hn"):
             put(f"gru.{g}.kernel", _orth(key(cell + (g,), 1), (H, H), 1.0))
-        put("post.kernel", _orth(key(("post_torso", "Dense_0"), 1), (H, H), s2))
-        put("head.kernel", _orth(key(("action_head", "Dense_0"), 1), (H, K), 0.01))
+        put("head.kernel", _orth(key(("action_head", "Dense_0"), 1), (named["head.kernel"].shape[0], K), 0.01))

@@ -24,6 +24,7 @@ import torch
 
 from magpo_amd import distributed as mdist
 from magpo_amd.actor import GruActor
+from magpo_amd.torso import DEFAULT_TORSO, torso_from_config
 from magpo_amd.config import Config, compose
 from magpo_amd.evaluator import get_eval_fn, get_num_eval_envs, make_rec_eval_act_fn
 from magpo_amd.learner import MagpoLearner, SystemConfig, host_split, prng_key
@@ -191,6 +192,16 @@ def get_learner_fn(env, apply_fns, update_fn, config):
     return learner_fn
 
 
+def actor_torsos(config):
+    """(pre, post) TorsoSpecs of ``network.actor_network`` (rec_magpo.py:570-571 instantiates them as MLPTorso); what the HIP
+    kernels do not cover raises NotImplementedError (magpo_amd/torso.py)."""
+    an = config.network.get("actor_network")
+    if an is None:
+        return DEFAULT_TORSO, DEFAULT_TORSO
+    return (torso_from_config(an.pre_torso) if "pre_torso" in an else DEFAULT_TORSO,
+            torso_from_config(an.post_torso) if "post_torso" in an else DEFAULT_TORSO)
+
+
 def learner_setup(env, keys, config, device=None, rank: int = 0, world: int = 1):
     """Initialise learner_fn, networks, optimiser, environments and states (rec_magpo.py:533-685)."""
     key, actor_net_key, net_key = keys
@@ -208,6 +219,7 @@ def learner_setup(env, keys, config, device=None, rank: int = 0, world: int = 1)
         raise NotImplementedError("memory_config.type must be rec_sable")
     if int(nc.embed_dim) not in (16, 32, 64, 128) or int(nc.n_head) not in (1, 2, 4) or int(config.network.hidden_state_dim) != 128:
         raise NotImplementedError("HIP kernels support embed_dim in {16,32,64,128}, n_head in {1,2,4}, hidden_state_dim=128 (any n_block)")
+    pre_torso, post_torso = actor_torsos(config)
     device = device or torch.device("cuda", torch.cuda.current_device())
     U = int(config.system.update_batch_size)
     # networks (rec_magpo.py:559-579), optimisers (:581-589) -- objects that own their kernels' device buffers
@@ -223,7 +235,8 @@ def learner_setup(env, keys, config, device=None, rank: int = 0, world: int = 1)
     sable_network = SableGuider(cfg.num_agents, cfg.num_actions, env.obs_dim, device, obs_ld=obs_ld, embed_dim=int(nc.embed_dim), n_head=int(nc.n_head),
                                 n_block=int(nc.n_block), decay_scaling_factor=float(mc.decay_scaling_factor),
                                 use_pe=bool(mc.timestep_positional_encoding), max_pos=cfg.time_limit + 1, seed=g_seed)
-    actor_network = GruActor(cfg.num_agents, cfg.num_actions, env.obs_dim, device, obs_ld=obs_ld, seed=a_seed, tuning=sable_network.tuning)
+    actor_network = GruActor(cfg.num_agents, cfg.num_actions, env.obs_dim, device, obs_ld=obs_ld, seed=a_seed, tuning=sable_network.tuning,
+                             pre_torso=pre_torso, post_torso=post_torso)
     guider_optim, actor_optim = ClipAdam(sable_network, sysc), ClipAdam(actor_network, sysc)
     # Pack apply and update functions (rec_magpo.py:624-632)
     apply_fns = (sable_network.get_actions, sable_network.apply, actor_network.apply)
@@ -250,7 +263,8 @@ def run_experiment(_config) -> float:
     learn, actor_network, learner_state = learner_setup(env, (key, actor_net_key, net_key), config, device, rank, world)
 
     from magpo_amd.learner import obs_row_stride
-    eval_actor = GruActor(env.num_agents, env.action_dim, env.obs_dim, device, obs_ld=obs_row_stride(env.cfg.obs_dim))
+    eval_actor = GruActor(env.num_agents, env.action_dim, env.obs_dim, device, obs_ld=obs_row_stride(env.cfg.obs_dim),
+                          pre_torso=actor_network.pre_spec, post_torso=actor_network.post_spec)
     eval_act_fn = make_rec_eval_act_fn(eval_actor, config)
     evaluator = get_eval_fn(eval_env, eval_act_fn, config, absolute_metric=False, device=device, n_devices=n_devices)
 
