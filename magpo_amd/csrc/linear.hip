@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256) void k_linear(const float* __restrict__ X, int
   }
 }
 
-// Wave-autonomous variant for KIN in {64, 128}: every wave owns 32*NCB output columns, keeps their weight
+// Wave-autonomous form for KIN in {64, 128} when a pre-activation copy is requested: every wave owns 32*NCB output columns, keeps their weight
 // fragments in VGPRs for the whole persistent loop and streams 32-row activation tiles straight from HBM
 // (each lane reads one contiguous half-row, a wave one contiguous 32 x KIN block).  No LDS, no barriers:
 // latency is hidden by several independent waves per SIMD.
@@ -335,81 +335,12 @@ __global__ __launch_bounds__(256) void k_linear_pro(ProArgs p, const float* __re
   }
 }
 
-// Wide-input variant (KIN = 192 / 256 / 384, the dX GEMMs of the fused projections and of the GRU input
-// layer): a wave owns 32 output columns and keeps ALL their weight fragments in VGPRs (KIN/2 registers);
-// activations stream in 64-wide k-chunks (one contiguous 128-B piece per lane and chunk).
-template <int KIN>
-__global__ __launch_bounds__(256) void k_linear_wk(const float* __restrict__ X, int ldx, const float* __restrict__ Wt,
-                                                   const float* __restrict__ bias, float* __restrict__ Y, int ldy,
-                                                   int R, int NOUT, int act) {
-  constexpr int NKC = KIN / 64;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 31, h = lane >> 5;
-  const int c0 = (blockIdx.y * (blockDim.x >> 6) + wave) * 32;
-  if (c0 >= NOUT) return;
-  const int n = c0 + lr;
-  float4 wf[NKC][8];
-#pragma unroll
-  for (int kc = 0; kc < NKC; ++kc)
-#pragma unroll
-    for (int u = 0; u < 8; ++u) wf[kc][u] = *reinterpret_cast<const float4*>(Wt + (long)n * KIN + kc * 64 + 32 * h + 4 * u);
-  const float bv = (bias && n < NOUT) ? bias[n] : 0.f;
-  const int ntiles = (R + 31) >> 5;
-  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const long row = (long)tile * 32 + lr;
-    const bool ok = row < R;
-    const float* xp = X + (ok ? row : 0) * (long)ldx + 32 * h;
-    f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    float4 af[2][8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) af[0][u] = ok ? *reinterpret_cast<const float4*>(xp + 4 * u) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int kc = 0; kc < NKC; ++kc) {
-      if (kc + 1 < NKC) {
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-          af[(kc + 1) & 1][u] = ok ? *reinterpret_cast<const float4*>(xp + (kc + 1) * 64 + 4 * u) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kc & 1][u].x, wf[kc][u].x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kc & 1][u].y, wf[kc][u].y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kc & 1][u].z, wf[kc][u].z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kc & 1][u].w, wf[kc][u].w, acc, 0, 0, 0);
-      }
-    }
-    if (act <= ACT_RELU && (long)tile * 32 + 32 <= R && c0 + 32 <= NOUT) {
-      // the common case (whole tile, plain / relu output): straight-line stores, no per-element exec masking
-      float* yp = Y + ((long)tile * 32 + 4 * h) * (long)ldy + n;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        float v = acc[i] + bv;
-        if (act == ACT_RELU) v = fmaxf(v, 0.f);
-        yp[(long)((i & 3) + 8 * (i >> 2)) * ldy] = v;
-      }
-    } else if (n < NOUT) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const long gr = (long)tile * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-        if (gr < R) {
-          float v = acc[i] + bv;
-          if (act == ACT_RELU) v = fmaxf(v, 0.f);
-          else if (act == ACT_GELU) v = gelu_tanh(v);
-          else if (act == ACT_SWISH) v = swishf_(v);
-          else if (act == ACT_TANH) v = tanhf(v);
-          Y[gr * (long)ldy + n] = v;
-        }
-      }
-    }
-  }
-}
-
-// Wide-input dense layer, second form: weights register-resident as in k_linear_wk, but the 32-row activation tile is
-// fetched ONCE per workgroup with fully coalesced loads and shared by the 4 waves through a double-buffered LDS tile.
-// k_linear_wk lets every wave fetch its own copy of the tile as per-lane 128-B row pieces: 64 cache lines touched by each
-// load instruction, 4096 line requests per tile and workgroup -- the L1 tag rate, not MFMA or HBM, bounds it (~50 % of the
-// MFMA peak).  Here a tile costs KIN/4 coalesced line requests and one barrier.
+// Shared-tile dense layer (every KIN in {64, ..., 384} when no pre-activation copy is requested): a wave owns 32 output columns and
+// keeps ALL their weight fragments in VGPRs (KIN/2 registers); the 32-row activation tile is fetched ONCE per workgroup with fully
+// coalesced loads and shared by the waves through a double-buffered LDS tile.  A wave-autonomous form, in which every wave fetched
+// its own copy of the tile as per-lane 128-B row pieces (64 cache lines touched by each load instruction, 4096 line requests per
+// tile and workgroup), was bound by the L1 tag rate, not MFMA or HBM (~50 % of the MFMA peak).  Here a tile costs KIN/4 coalesced
+// line requests and one barrier.
 template <int KIN, int NW, bool BF3 = false>
 __global__ __launch_bounds__(64 * NW) void k_linear_lds(const float* __restrict__ X, int ldx, const float* __restrict__ Wt,
                                                     const float* __restrict__ bias, float* __restrict__ Y, int ldy,
@@ -1119,9 +1050,9 @@ __global__ __launch_bounds__(256, 1) void k_wgrad_full_x(const float* __restrict
 
 // Whole-matrix weight gradient on a 2 x 2 wave grid, every tile full: a workgroup accumulates (64 KTW) weight rows x (64 NTW)
 // columns (wave = (k half, column half): 32 KTW rows x 32 NTW columns, KTW x NTW accumulator tiles); blockIdx.y selects the column block.
-//   KTW = 1: 64 x 192 (the retention K/V/G projection of the cross site) -- the split kernel reads X twice for this shape;
-//   KTW = 2: 128 x 384 as two column halves: X is read twice (+25 % bytes), but the tiles take 80 KB and the accumulators
-//            96 registers, so TWO workgroups share a CU and one's barrier / stash phases run under the other's MFMAs.
+//   <1,3>: 64 x 192 (the retention K/V/G projection of the cross site) -- the split kernel reads X twice for this shape;
+//   <2,2>: 128 x 128.
+// Both take 64 KB of tiles, so TWO workgroups share a CU and one's barrier / stash phases run under the other's MFMAs.
 // Same pipeline as k_wgrad_full_x (uniform-base tile loads, operands one k-step ahead, bias sums at stash time), unpadded tiles.
 template <int KTW, int NTW>
 __global__ __launch_bounds__(256, 2) void k_wgrad_full_g(const float* __restrict__ X, int ldx, const float* __restrict__ dY, int ldy,
@@ -1233,15 +1164,24 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_full_g(const float* __restrict
 
 using namespace magpo;
 
+// Kernel K, with its dynamic-LDS limit raised to `lds` bytes when that exceeds the 64 KB default (once per kernel: every
+// launch of one instance asks for the same size).
+template <auto K>
+static auto with_lds(size_t lds) {
+  static bool done = false;
+  if (!done && lds > 65536) {
+    hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    done = true;
+  }
+  return K;
+}
+
 extern "C" int magpo_linear(const float* X, int ldx, const float* Wt, const float* bias, float* Y, int ldy, float* Ypre,
                             long R, int KIN, int NOUT, int act, int variant, hipStream_t stream) {
   if (R <= 0) return MAGPO_OK;
   if ((ldx & 3) || KIN % 64 || NOUT <= 0) { set_error("magpo_linear: KIN must be a multiple of 64, ldx of 4"); return MAGPO_EINVAL; }
-  // variant (A/B reference paths, same results up to fp32 summation order; 0 = the fast path): bit 0 = wave-autonomous k_linear_wk instead of
-  // the shared-tile k_linear_lds, bit 1 = the same for KIN = 64 only
-  // bit 2 = bf16 triples (k_linear_lds<.., BF3>: KIN 128 / 192 on the shared-tile path; ignored elsewhere)
-  if (variant < 0 || variant > 7) { set_error("magpo_linear: variant must be in [0, 7]"); return MAGPO_EINVAL; }
-  const bool lds64 = !(variant & 2);
+  // variant 4 = bf16 triples (k_linear_lds<KIN, 4, true>: KIN 128 / 192 with four-wave column blocks; ignored elsewhere)
+  if (variant != 0 && variant != 4) { set_error("magpo_linear: variant must be 0 or 4"); return MAGPO_EINVAL; }
   const float* aux = nullptr;
   if (act < ACT_NONE || act > ACT_TANHBWD) { set_error("magpo_linear: act must be in [0, 6]"); return MAGPO_EINVAL; }
   if (act == ACT_MASKPOS || act == ACT_TANHBWD) {   // the Ypre argument carries the mask INPUT (same shape / stride as Y), nothing else is written
@@ -1249,69 +1189,35 @@ extern "C" int magpo_linear(const float* X, int ldx, const float* Wt, const floa
     aux = Ypre;
     Ypre = nullptr;
   }
-  if (act == ACT_TANHBWD) {   // only the shared-tile kernels read the mask
-    if (KIN != 64 && KIN != 128 && KIN != 192 && KIN != 256 && KIN != 384) { set_error("magpo_linear: act 6 needs KIN in {64, 128, 192, 256, 384}"); return MAGPO_EINVAL; }
-    variant &= 4;
-  }
-  if ((KIN == 128 || KIN == 192 || KIN == 256 || KIN == 384 || (KIN == 64 && lds64)) && !Ypre) {
-    // persistent waves: one wave per (walker, 32-column group); blocks of 4 / 2 / 1 waves so that every wave slot of
-    // a CU can be filled (a 3-wave block leaves a quarter of the slots idle), about one resident wave set in total
+  const bool shared_tile = KIN == 64 || KIN == 128 || KIN == 192 || KIN == 256 || KIN == 384;
+  if (act == ACT_TANHBWD && !shared_tile) { set_error("magpo_linear: act 6 needs KIN in {64, 128, 192, 256, 384}"); return MAGPO_EINVAL; }
+  if (shared_tile && !Ypre) {
+    // shared-tile form: 4 waves per block, 2 when the column groups do not fill blocks of 4 (every wave then has MFMA work);
+    // column groups past NOUT idle in the MFMA part but help loading
     const int ncg = (NOUT + 31) / 32;
-    const int wpb = (ncg % 4 == 0) ? 4 : ((ncg % 2 == 0) ? 2 : 1);
+    const int nw = (ncg % 4 == 0) ? 4 : 2;
+    const int gy = (ncg + nw - 1) / nw;
     const long ntiles = (R + 31) / 32;
-    long walkers = 2048 / wpb;
-    if (walkers > ntiles) walkers = ntiles;
-    dim3 grid((unsigned)walkers, (unsigned)(ncg / wpb)), block(64 * wpb);
-    const bool use_lds = !(variant & 1);
-    if (use_lds) {
-      // shared-tile form: 4 waves per block, 2 when the column groups do not fill blocks of 4 (every wave then has MFMA work);
-      // column groups past NOUT idle in the MFMA part but help loading
-      const int nw = (ncg % 4 == 0) ? 4 : 2;
-      const int gy = (ncg + nw - 1) / nw;
-      long wk2 = 2048 / nw;   // about 2 waves per SIMD; LDS 2 x 32 x (KIN + 4) floats per block
-      // several column blocks per row walker: all of them co-resident (walkers x column blocks <= resident workgroups), so the
-      // column blocks of a walker -- same XCD, since the walker count is a multiple of 8 -- read a tile at about the same
-      // time and the re-reads hit that XCD's L2 instead of HBM (in a second round they would come from HBM again)
-      if (gy >= 3) wk2 /= 2;
-      if (wk2 > ntiles) wk2 = ntiles;
-      dim3 g2((unsigned)wk2, (unsigned)gy), b2(64 * nw);
-      if ((variant & 4) && (KIN == 128 || KIN == 192) && nw == 4) {   // (two-wave blocks -- narrow outputs -- are slower on it: 128 -> 20 0.86 vs 1.35 ms)
-        const size_t ldb = (size_t)2 * 3 * 32 * (KIN + 8) * sizeof(__bf16);
-#define LAUNCH_BF3(K_)                                                                                                  \
-        {                                                                                                               \
-          static bool attr = false;                                                                                     \
-          if (!attr && ldb > 65536) {                                                                                   \
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_linear_lds<K_, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldb); \
-            attr = true;                                                                                                \
-          }                                                                                                             \
-          hipLaunchKernelGGL((k_linear_lds<K_, 4, true>), g2, b2, ldb, stream, X, ldx, Wt, bias, Y, ldy, (int)R, NOUT, act, aux); \
-        }
-        if (KIN == 128) LAUNCH_BF3(128) else LAUNCH_BF3(192)
-#undef LAUNCH_BF3
-        return check_launch("magpo_linear");
-      }
-      const size_t lds = (size_t)2 * 32 * (KIN + LDP) * sizeof(float);
-#define LAUNCH_LDS(K_)                                                                                                   \
-      {                                                                                                                 \
-        static bool attr = false;                                                                                       \
-        if (!attr && lds > 65536) {                                                                                     \
-          hipFuncSetAttribute(reinterpret_cast<const void*>(&k_linear_lds<K_, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-          hipFuncSetAttribute(reinterpret_cast<const void*>(&k_linear_lds<K_, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-          attr = true;                                                                                                  \
-        }                                                                                                               \
-        if (nw == 4) hipLaunchKernelGGL((k_linear_lds<K_, 4>), g2, b2, lds, stream, X, ldx, Wt, bias, Y, ldy, (int)R, NOUT, act, aux); \
-        else hipLaunchKernelGGL((k_linear_lds<K_, 2>), g2, b2, lds, stream, X, ldx, Wt, bias, Y, ldy, (int)R, NOUT, act, aux); \
-      }
-      if (KIN == 64) LAUNCH_LDS(64) else if (KIN == 128) LAUNCH_LDS(128) else if (KIN == 192) LAUNCH_LDS(192) else if (KIN == 256) LAUNCH_LDS(256) else LAUNCH_LDS(384)
-#undef LAUNCH_LDS
-      return check_launch("magpo_linear");
-    }
-    if (KIN == 128) hipLaunchKernelGGL((k_linear_wk<128>), grid, block, 0, stream, X, ldx, Wt, bias, Y, ldy, (int)R, NOUT, act);
-    else if (KIN == 192) hipLaunchKernelGGL((k_linear_wk<192>), grid, block, 0, stream, X, ldx, Wt, bias, Y, ldy, (int)R, NOUT, act);
-    else if (KIN == 256) hipLaunchKernelGGL((k_linear_wk<256>), grid, block, 0, stream, X, ldx, Wt, bias, Y, ldy, (int)R, NOUT, act);
-    else hipLaunchKernelGGL((k_linear_wk<384>), grid, block, 0, stream, X, ldx, Wt, bias, Y, ldy, (int)R, NOUT, act);
+    long wk2 = 2048 / nw;   // about 2 waves per SIMD; LDS 2 x 32 x (KIN + 4) floats per block
+    // several column blocks per row walker: all of them co-resident (walkers x column blocks <= resident workgroups), so the
+    // column blocks of a walker -- same XCD, since the walker count is a multiple of 8 -- read a tile at about the same
+    // time and the re-reads hit that XCD's L2 instead of HBM (in a second round they would come from HBM again)
+    if (gy >= 3) wk2 /= 2;
+    if (wk2 > ntiles) wk2 = ntiles;
+    // (two-wave blocks -- narrow outputs -- are slower on bf16 triples: 128 -> 20 0.86 vs 1.35 ms)
+    const bool bf3 = variant == 4 && (KIN == 128 || KIN == 192) && nw == 4;
+    const size_t lds = bf3 ? (size_t)2 * 3 * 32 * (KIN + 8) * sizeof(__bf16) : (size_t)2 * 32 * (KIN + LDP) * sizeof(float);
+    decltype(&k_linear_lds<64, 4>) k;
+    if (bf3) k = KIN == 128 ? with_lds<k_linear_lds<128, 4, true>>(lds) : with_lds<k_linear_lds<192, 4, true>>(lds);
+    else if (KIN == 64) k = nw == 4 ? with_lds<k_linear_lds<64, 4>>(lds) : with_lds<k_linear_lds<64, 2>>(lds);
+    else if (KIN == 128) k = nw == 4 ? with_lds<k_linear_lds<128, 4>>(lds) : with_lds<k_linear_lds<128, 2>>(lds);
+    else if (KIN == 192) k = nw == 4 ? with_lds<k_linear_lds<192, 4>>(lds) : with_lds<k_linear_lds<192, 2>>(lds);
+    else if (KIN == 256) k = nw == 4 ? with_lds<k_linear_lds<256, 4>>(lds) : with_lds<k_linear_lds<256, 2>>(lds);
+    else k = nw == 4 ? with_lds<k_linear_lds<384, 4>>(lds) : with_lds<k_linear_lds<384, 2>>(lds);
+    hipLaunchKernelGGL(k, dim3((unsigned)wk2, (unsigned)gy), dim3(64 * nw), lds, stream, X, ldx, Wt, bias, Y, ldy, (int)R, NOUT, act, aux);
     return check_launch("magpo_linear");
   }
+  // a pre-activation copy is requested
   if (KIN == 64 || KIN == 128) {
     // wave-autonomous path: 64 columns per wave, up to 4 waves (256 columns) per workgroup
     const int cpw = KIN == 64 ? 64 : 32;  // columns per wave (128 per wave was measured slower: 256 VGPRs + spills)
@@ -1326,26 +1232,13 @@ extern "C" int magpo_linear(const float* X, int ldx, const float* Wt, const floa
     else hipLaunchKernelGGL((k_linear_w<128, 1>), grid, block, 0, stream, X, ldx, Wt, bias, Y, ldy, Ypre, (int)R, NOUT, act);
     return check_launch("magpo_linear");
   }
-  dim3 grid((unsigned)((R + 63) / 64)), block(256);
-  size_t lds = (size_t)64 * (KIN + LDP) * sizeof(float);
-#define LAUNCH(K_)                                                                                              \
-  if (lds > 65536) {                                                                                            \
-    static bool attr_set = false;                                                                               \
-    if (!attr_set) {                                                                                            \
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_linear<K_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-      attr_set = true;                                                                                          \
-    }                                                                                                           \
-  }                                                                                                             \
-  hipLaunchKernelGGL(k_linear<K_>, grid, block, lds, stream, X, ldx, Wt, bias, Y, ldy, Ypre, (int)R, NOUT, act)
-  switch (KIN) {
-    case 64: LAUNCH(64); break;
-    case 128: LAUNCH(128); break;
-    case 192: LAUNCH(192); break;
-    case 256: LAUNCH(256); break;
-    case 384: LAUNCH(384); break;
-    default: set_error("magpo_linear: unsupported KIN"); return MAGPO_EINVAL;
-  }
-#undef LAUNCH
+  const size_t lds = (size_t)64 * (KIN + LDP) * sizeof(float);
+  decltype(&k_linear<192>) k;
+  if (KIN == 192) k = with_lds<k_linear<192>>(lds);
+  else if (KIN == 256) k = with_lds<k_linear<256>>(lds);
+  else if (KIN == 384) k = with_lds<k_linear<384>>(lds);
+  else { set_error("magpo_linear: unsupported KIN"); return MAGPO_EINVAL; }
+  hipLaunchKernelGGL(k, dim3((unsigned)((R + 63) / 64)), dim3(256), lds, stream, X, ldx, Wt, bias, Y, ldy, Ypre, (int)R, NOUT, act);
   return check_launch("magpo_linear");
 }
 
@@ -1382,105 +1275,43 @@ extern "C" long magpo_wgrad_workspace_floats(int KIN, int NOUT, int G) { return 
 extern "C" int magpo_wgrad(const float* X, int ldx, const float* dY, int ldy, long R, int KIN, int krows, int NOUT, float* dW,
                            float* db, float* workspace, int G, float scale, int accumulate, int variant, hipStream_t stream) {
   if ((ldx & 3) || (ldy & 3) || KIN % 64) { set_error("magpo_wgrad: bad strides / KIN"); return MAGPO_EINVAL; }
-  // variant (A/B reference paths, same results up to fp32 summation order; 0 = the fast path), bit mask: 1 = split kernel k_wgrad for every
-  // shape, 2 = generic k_wgrad_full also on full tiles, 4 = no unpadded-tile 64 x 256 kernel, 8 = 128 x 384 as two column halves on the
-  // wave-grid kernel, 16 = 64 x 64 on the wave-grid kernel, 32 = 64 x 256 on the wave-grid kernel
-  if (variant < 0 || variant > 127) { set_error("magpo_wgrad: variant must be in [0, 127]"); return MAGPO_EINVAL; }
-  float* slab = workspace;
-  float* bslab = db ? workspace + (long)G * KIN * NOUT : nullptr;
-  const bool use_full = !(variant & 1);
-  const bool use_x = !(variant & 2);
+  // variant 64 = 128 x 384 on bf16 MFMA with three-piece operand splits (k_wgrad_full_x<4, 3, LDP, true>, every tile full; ignored elsewhere)
+  if (variant != 0 && variant != 64) { set_error("magpo_wgrad: variant must be 0 or 64"); return MAGPO_EINVAL; }
   // whole-matrix form: one workgroup per slab accumulates the full KIN x NOUT block, every row read once.  128x384 always
   // (k_wgrad_full, or k_wgrad_full_x when every tile is full); with full tiles also 128x128 (two workgroups per CU: 1.53 ->
-  // 1.30 ms) and 64x256 (1.84 -> 1.76 ms).  Other shapes stay on the split kernel k_wgrad.
-  const bool exact = R % 64 == 0 && use_x;
-  const bool use_pad0 = !(variant & 4);
-  const int g_alt = (variant >> 4) & 3;   // experiments (bit mask): 1 = 64x64 on the wave-grid kernel (0.43 vs 0.40 ms), 2 = 64x256 (1.63 vs 1.64 ms)
-  if (use_full && exact && use_pad0 && !(g_alt & 2) && KIN == 64 && NOUT == 256 && R >= 64 * 256) {
+  // 1.30 ms), 64x256 (1.84 -> 1.76 ms) and 64x192.  Other shapes stay on the split kernel k_wgrad.  Measured and not kept:
+  // 128x384 as two column halves on the wave-grid kernel (3.57 vs 3.63 ms while reading X twice: within noise), 64x64 and
+  // 64x256 on the wave-grid kernel (0.43 vs 0.40 ms, 1.63 vs 1.64 ms).
+  const bool exact = R % 64 == 0, big = R >= 64 * 256;
+  const size_t lds_full = (size_t)64 * (KIN + NOUT) * sizeof(float), lds_pad = (size_t)64 * ((KIN + LDP) + (NOUT + LDP)) * sizeof(float);
+  auto bias_slab = [&] { return db ? workspace + (long)G * KIN * NOUT : nullptr; };   // after G is final
+  if (big && exact && KIN == 64 && NOUT == 256) {   // unpadded tiles: exactly 80 KB, two workgroups per CU
     if (G > 512) G = 512;
-    float* bsl = db ? workspace + (long)G * KIN * NOUT : nullptr;
-    const size_t lds = (size_t)64 * (KIN + NOUT) * sizeof(float);
-    static bool attrp = false;
-    if (!attrp) { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad_full_x<2, 2, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attrp = true; }
-    hipLaunchKernelGGL((k_wgrad_full_x<2, 2, 0>), dim3(G), dim3(256), lds, stream, X, ldx, dY, ldy, (int)R, slab, bsl);
-    long P = (long)krows * NOUT;
-    hipLaunchKernelGGL(k_reduce_slabs, dim3((unsigned)((P + 63) / 64)), dim3(1024), 0, stream, slab, dW, G, P, (long)KIN * NOUT, scale, accumulate);
-    if (db) hipLaunchKernelGGL(k_reduce_slabs, dim3((NOUT + 63) / 64), dim3(1024), 0, stream, bsl, db, G, (long)NOUT, (long)NOUT, scale, accumulate);
-    return check_launch("magpo_wgrad");
-  }
-  // 128 x 384 on this kernel (two column halves, two workgroups per CU) measured 3.57 vs 3.63 ms for k_wgrad_full_x<4,3> while
-  // reading X twice: within noise, so the one-pass kernel stays the default (variant bit 3 selects this one)
-  const int use_g2 = (variant >> 3) & 1;
-  int gk = 0, gn = 0;   // (KTW, NTW) of the 2 x 2 wave-grid kernel, 0 = not this kernel
-  if (KIN == 64 && NOUT == 192) { gk = 1; gn = 3; }
-  else if (use_g2 && KIN == 128 && NOUT == 384) { gk = 2; gn = 3; }
-  else if ((g_alt & 1) && KIN == 64 && NOUT == 64) { gk = 1; gn = 1; }
-  else if ((g_alt & 2) && KIN == 64 && NOUT == 256) { gk = 1; gn = 4; }
-  else if (KIN == 128 && NOUT == 128) { gk = 2; gn = 2; }        // 1.23 vs 1.32 ms for k_wgrad_full_x<4,1>
-  if (use_full && exact && R >= 64 * 256 && gk) {
-    const int nbk = 64 * gn, gy = NOUT / nbk;
-    const size_t lds = (size_t)64 * (KIN + nbk) * sizeof(float);
-    const int per_cu = lds <= 32 * 1024 ? 4 : (lds <= 40 * 1024 ? 3 : 2);   // resident workgroups per CU (LDS; launch bound 2 waves / SIMD for the wide ones)
-    const int gcap = 256 * per_cu / gy;
-    if (G > gcap) G = gcap;
-    float* bsl = db ? workspace + (long)G * KIN * NOUT : nullptr;
-#define LAUNCH_G(K_, N_)                                                                                                      \
-    {                                                                                                                          \
-      static bool attr = false;                                                                                                \
-      if (!attr) { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad_full_g<K_, N_>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * (64 * K_ + 64 * N_) * 4); attr = true; } \
-      hipLaunchKernelGGL((k_wgrad_full_g<K_, N_>), dim3(G, gy), dim3(256), lds, stream, X, ldx, dY, ldy, (int)R, NOUT, slab, bsl); \
-    }
-    if (gk == 1 && gn == 3) LAUNCH_G(1, 3) else if (gk == 2 && gn == 3) LAUNCH_G(2, 3) else if (gk == 1 && gn == 1) LAUNCH_G(1, 1)
-    else if (gk == 1 && gn == 4) LAUNCH_G(1, 4) else LAUNCH_G(2, 2)
-#undef LAUNCH_G
-    long P = (long)krows * NOUT;
-    hipLaunchKernelGGL(k_reduce_slabs, dim3((unsigned)((P + 63) / 64)), dim3(1024), 0, stream, slab, dW, G, P, (long)KIN * NOUT, scale, accumulate);
-    if (db) hipLaunchKernelGGL(k_reduce_slabs, dim3((NOUT + 63) / 64), dim3(1024), 0, stream, bsl, db, G, (long)NOUT, (long)NOUT, scale, accumulate);
-    return check_launch("magpo_wgrad");
-  }
-  const bool full_shape = (KIN == 128 && NOUT == 384) || (exact && ((KIN == 128 && NOUT == 128) || (KIN == 64 && NOUT == 256)));
-  if (use_full && full_shape && R >= 64 * 256) {
-    const int gcap = (KIN == 128 && NOUT == 128) ? 512 : 256;
-    if (G > gcap) G = gcap;
-    float* bsl = db ? workspace + (long)G * KIN * NOUT : nullptr;
-    const size_t lds = (size_t)64 * ((KIN + LDP) + (NOUT + LDP)) * sizeof(float);
-#define LAUNCH_FULL(KT_, NT_)                                                                                                 \
-    {                                                                                                                          \
-      static bool attr = false;                                                                                                \
-      if (!attr) { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad_full<KT_, NT_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; } \
-      static bool attrx = false;                                                                                               \
-      if (!attrx) { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad_full_x<KT_, NT_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attrx = true; } \
-      if (R % 64 == 0 && use_x) hipLaunchKernelGGL((k_wgrad_full_x<KT_, NT_>), dim3(G), dim3(256), lds, stream, X, ldx, dY, ldy, (int)R, slab, bsl); \
-      else hipLaunchKernelGGL((k_wgrad_full<KT_, NT_>), dim3(G), dim3(256), lds, stream, X, ldx, dY, ldy, (int)R, slab, bsl);  \
-    }
-    if ((variant & 64) && KIN == 128 && NOUT == 384 && R % 64 == 0 && use_x) {   // bf16 triples (k_wgrad_full_x<4, 3, LDP, true>)
-      static bool attrb = false;
-      if (!attrb) { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad_full_x<4, 3, LDP, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attrb = true; }
-      hipLaunchKernelGGL((k_wgrad_full_x<4, 3, LDP, true>), dim3(G), dim3(256), lds, stream, X, ldx, dY, ldy, (int)R, slab, bsl);
-    } else
-    if (KIN == 64 && NOUT == 128) LAUNCH_FULL(2, 1) else if (KIN == 64 && NOUT == 256) LAUNCH_FULL(2, 2) else if (KIN == 64) LAUNCH_FULL(2, 3)
-    else if (NOUT == 128) LAUNCH_FULL(4, 1) else if (NOUT == 256) LAUNCH_FULL(4, 2) else LAUNCH_FULL(4, 3)
-#undef LAUNCH_FULL
-    long P = (long)krows * NOUT;
-    hipLaunchKernelGGL(k_reduce_slabs, dim3((unsigned)((P + 63) / 64)), dim3(1024), 0, stream, slab, dW, G, P, (long)KIN * NOUT, scale, accumulate);
-    if (db) hipLaunchKernelGGL(k_reduce_slabs, dim3((NOUT + 63) / 64), dim3(1024), 0, stream, bsl, db, G, (long)NOUT, (long)NOUT, scale, accumulate);
-    return check_launch("magpo_wgrad");
-  }
-  int nb = NOUT >= 128 ? 2 : 1;
-  // fill the chip in whole waves of workgroups: 3 (NB=2) / 4 (NB=1) resident workgroups per CU x 256 CUs
-  {
+    auto k = with_lds<k_wgrad_full_x<2, 2, 0>>(lds_full);
+    hipLaunchKernelGGL(k, dim3(G), dim3(256), lds_full, stream, X, ldx, dY, ldy, (int)R, workspace, bias_slab());
+  } else if (big && exact && ((KIN == 64 && NOUT == 192) || (KIN == 128 && NOUT == 128))) {
+    // 2 x 2 wave grid, one column block; 64 KB of LDS: two resident workgroups per CU.  128x128: 1.23 vs 1.32 ms for k_wgrad_full_x<4,1>
+    if (G > 512) G = 512;
+    auto k = KIN == 64 ? with_lds<k_wgrad_full_g<1, 3>>(lds_full) : with_lds<k_wgrad_full_g<2, 2>>(lds_full);
+    hipLaunchKernelGGL(k, dim3(G, 1), dim3(256), lds_full, stream, X, ldx, dY, ldy, (int)R, NOUT, workspace, bias_slab());
+  } else if (big && KIN == 128 && NOUT == 384) {
+    if (G > 256) G = 256;
+    auto k = !exact ? with_lds<k_wgrad_full<4, 3>>(lds_pad)
+                    : variant == 64 ? with_lds<k_wgrad_full_x<4, 3, LDP, true>>(lds_pad) : with_lds<k_wgrad_full_x<4, 3>>(lds_pad);
+    hipLaunchKernelGGL(k, dim3(G), dim3(256), lds_pad, stream, X, ldx, dY, ldy, (int)R, workspace, bias_slab());
+  } else {
+    const int nb = NOUT >= 128 ? 2 : 1;
+    // fill the chip in whole waves of workgroups: 3 (NB=2) / 4 (NB=1) resident workgroups per CU x 256 CUs
     const int per_g = ((NOUT + 64 * nb - 1) / (64 * nb)) * (KIN / 64);
-    const int resident = 256 * (nb == 2 ? 3 : 4);
-    int g_fit = resident / per_g;
+    int g_fit = 256 * (nb == 2 ? 3 : 4) / per_g;
     if (g_fit < 1) g_fit = 1;
     if (G > g_fit) G = g_fit;
+    dim3 grid(G, (NOUT + 64 * nb - 1) / (64 * nb), KIN / 64);
+    hipLaunchKernelGGL(nb == 2 ? k_wgrad<2> : k_wgrad<1>, grid, dim3(256), 0, stream, X, ldx, dY, ldy, (int)R, KIN, NOUT, workspace, bias_slab());
   }
-  dim3 grid(G, (NOUT + 64 * nb - 1) / (64 * nb), KIN / 64), block(256);
-  if (nb == 2) hipLaunchKernelGGL(k_wgrad<2>, grid, block, 0, stream, X, ldx, dY, ldy, (int)R, KIN, NOUT, slab, bslab);
-  else hipLaunchKernelGGL(k_wgrad<1>, grid, block, 0, stream, X, ldx, dY, ldy, (int)R, KIN, NOUT, slab, bslab);
-  long P = (long)krows * NOUT;
-  hipLaunchKernelGGL(k_reduce_slabs, dim3((unsigned)((P + 63) / 64)), dim3(1024), 0, stream, slab, dW, G, P, (long)KIN * NOUT, scale, accumulate);
-  if (db) hipLaunchKernelGGL(k_reduce_slabs, dim3((NOUT + 63) / 64), dim3(1024), 0, stream, bslab, db, G, (long)NOUT, (long)NOUT, scale, accumulate);
+  const long P = (long)krows * NOUT;
+  hipLaunchKernelGGL(k_reduce_slabs, dim3((unsigned)((P + 63) / 64)), dim3(1024), 0, stream, workspace, dW, G, P, (long)KIN * NOUT, scale, accumulate);
+  if (db) hipLaunchKernelGGL(k_reduce_slabs, dim3((NOUT + 63) / 64), dim3(1024), 0, stream, bias_slab(), db, G, (long)NOUT, (long)NOUT, scale, accumulate);
   return check_launch("magpo_wgrad");
 }
 

@@ -12,13 +12,11 @@ Environment variables are read HERE, once, when the default instance is built (A
                                 tests/test_kernels_gpu.py::test_gru_scan_bf16_triples_keep_fp32_accuracy), backward on fp32 MFMA; 0 = fp32 MFMA everywhere;
                                 1 = pairs (16 mantissa bits, forward and backward; never a default)
     MAGPO_GRU_BLOCK_ROWS=32|64  recurrent rows per workgroup of the fp32 GRU scans (default: by size)
-    MAGPO_LINEAR_LDS=0          wave-autonomous dense kernels instead of the shared-tile ones (MAGPO_LINEAR_LDS64=0: KIN = 64 only)
     MAGPO_LINEAR_BF3=1          dense layers with 128 / 192 inputs (four-wave column blocks) on bf16 MFMA with three-piece operand splits (24 mantissa bits,
                                 error against fp64 no larger than the fp32-MFMA kernel's, test_linear_bf16_triples_keep_fp32_accuracy).  OPT-IN: on the
                                 3x30-50 sweep the runs with it on the actor ended at 90.5 (ten seeds) against 93.4 without
                                 (profiles/r03_sweep_return_at_10M.md) -- not understood, so not a default
-    MAGPO_WGRAD_FULL=0 / MAGPO_WGRAD_FULL_X=0 / MAGPO_WGRAD_PAD0=0 / MAGPO_WGRAD_G2=1 / MAGPO_WGRAD_GALT=1|2|3 / MAGPO_WGRAD_BF3=1 (128 x 384 on bf16 triples: opt-in,
-                                its accumulation error is 1.2 x the fp32-MFMA kernel's)
+    MAGPO_WGRAD_BF3=1           the 128 x 384 weight gradient on bf16 triples: opt-in, its accumulation error is 1.2 x the fp32-MFMA kernel's
     MAGPO_ACT_EPW=4|8|16        envs per wave of the fused acting kernel (default: by size)
 """
 from __future__ import annotations
@@ -32,24 +30,20 @@ class Tuning:
     ret_chunk_tokens: int = 0     # 0 = default (32), 32 or 64: magpo_retention_num_chunks / _chunk_fwd / _chunk_bwd
     gru_split_bf16: int = 2       # magpo_gru_scan_fwd / _bwd (2: forward scan on bf16 triples = fp32 accuracy, see above; 0: fp32 MFMA)
     gru_block_rows: int = 0       # magpo_gru_scan_fwd / _bwd / magpo_gru_carry
-    linear_variant: int = 0       # magpo_linear of the guider (bit mask, see include/magpo.h; bit 2 = bf16 triples for KIN 128 / 192)
+    linear_variant: int = 0       # magpo_linear of the guider (0, or 4 = bf16 triples for KIN 128 / 192; see include/magpo.h)
     actor_linear_variant: int = 0 # magpo_linear of the GRU actor
-    wgrad_variant: int = 0        # magpo_wgrad (bit mask)
+    wgrad_variant: int = 0        # magpo_wgrad (0, or 64 = bf16 triples for 128 x 384)
     act_envs_per_wave: int = 0    # magpo_sable_act dims[11]
 
     @classmethod
     def from_env(cls, env=None) -> "Tuning":
         e = os.environ if env is None else env
-        off = lambda name: e.get(name) not in (None, "") and int(e[name]) == 0
         on = lambda name: e.get(name) not in (None, "") and int(e[name]) != 0
         t = cls()
         t.ret_chunk_tokens = 64 if e.get("MAGPO_RET_CHUNK") == "64" else 0
         t.gru_split_bf16 = int(e["MAGPO_GRU_SPLIT_BF16"]) if e.get("MAGPO_GRU_SPLIT_BF16") in ("0", "1", "2") else cls().gru_split_bf16
         t.gru_block_rows = int(e.get("MAGPO_GRU_BLOCK_ROWS", 0)) if e.get("MAGPO_GRU_BLOCK_ROWS") in ("32", "64") else 0
-        base = (1 if off("MAGPO_LINEAR_LDS") else 0) | (2 if off("MAGPO_LINEAR_LDS64") else 0)
-        t.linear_variant = base | (4 if on("MAGPO_LINEAR_BF3") else 0)
-        t.actor_linear_variant = base | (4 if on("MAGPO_LINEAR_BF3") else 0)
-        t.wgrad_variant = ((1 if off("MAGPO_WGRAD_FULL") else 0) | (2 if off("MAGPO_WGRAD_FULL_X") else 0) | (4 if off("MAGPO_WGRAD_PAD0") else 0)
-                           | (8 if on("MAGPO_WGRAD_G2") else 0) | ((int(e.get("MAGPO_WGRAD_GALT", 0)) & 3) << 4) | (64 if on("MAGPO_WGRAD_BF3") else 0))
+        t.linear_variant = t.actor_linear_variant = 4 if on("MAGPO_LINEAR_BF3") else 0
+        t.wgrad_variant = 64 if on("MAGPO_WGRAD_BF3") else 0
         t.act_envs_per_wave = int(e["MAGPO_ACT_EPW"]) if e.get("MAGPO_ACT_EPW") in ("4", "8", "16") else 0
         return t

@@ -42,6 +42,11 @@ def test_no_setters_and_no_environment_reads(built):
     # per-call knobs are validated, not remembered
     with pytest.raises(ValueError):
         built.call("magpo_retention_chunk_fwd", None, 64, None, 64, None, 64, None, 64, None, None, None, None, None, 1, 8, 4, 1, 0.5, 64, None, 48, None)
+    # the dense-layer variants are 0 or the bf16-triple bit (4 / 64); anything else is rejected before a pointer is touched
+    with pytest.raises(ValueError):
+        built.call("magpo_linear", None, 64, None, None, None, 64, None, 1, 64, 64, 0, 1, None)
+    with pytest.raises(ValueError):
+        built.call("magpo_wgrad", None, 64, None, 64, 1, 64, 64, 64, None, None, None, 1, 1.0, 0, 1, None)
 
 
 def test_no_torch_types_and_plain_c_header():

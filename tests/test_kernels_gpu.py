@@ -61,7 +61,10 @@ def test_linear(L, stream, KIN, NOUT, R, act):
     close(Y[:, :NOUT], ref, what="act")
 
 
-@pytest.mark.parametrize("KIN,NOUT,R", [(64, 64, 1000), (64, 256, 333), (128, 384, 200), (64, 20, 500), (256, 64, 100)])
+@pytest.mark.parametrize("KIN,NOUT,R", [(64, 64, 1000), (64, 256, 333), (128, 384, 200), (64, 20, 500), (256, 64, 100),
+                                      # one run of each whole-matrix kernel (>= 64 * 256 rows): full_x<2,2,0>, full_g<1,3>, full_g<2,2>,
+                                      # full_x<4,3>, full<4,3> (ragged last tile)
+                                      (64, 256, 16384), (64, 192, 16384), (128, 128, 16384), (128, 384, 16384), (128, 384, 16416)])
 def test_wgrad(L, stream, KIN, NOUT, R):
     g = torch.Generator().manual_seed(2)
     X = torch.randn(R, KIN, generator=g)
