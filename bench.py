@@ -10,6 +10,10 @@ both networks (forward, fused losses, hand-written backward, gradient all-reduce
 Nothing is skipped.  value = n_gpus * num_envs * rollout_length * K / wall (the reference's steps_per_second,
 rec_magpo.py:720-726,761), inputs resident in HBM, weak scaling (per-GPU envs fixed).
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps (with the per-kernel table and roofline those steps and the set-up's
+eager step yield), dumps its outputs if asked and prints the line.  ``--full`` adds what needs runs of its own after
+the timed region: the fp32-MFMA / dense-first-layers variants and the CPU oracle baseline (one GPU only).
 """
 from __future__ import annotations
 
@@ -341,9 +345,11 @@ def main():
     ap.add_argument("--n-head", type=int, default=1)
     ap.add_argument("--n-block", type=int, default=0, help="0 = the workload's default (1; coordsum-8x15: 2)")
     ap.add_argument("--ppo-epochs", type=int, default=0, help="0 = the reference default 4")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also measure the fp32-MFMA / dense-first-layers variants and "
+                    "the CPU oracle baseline (one GPU only; ~40 s more)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
     ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--no-variants", action="store_true", help="skip the fp32-MFMA / dense-first-layers variant measurements after the timed region")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the fp32-MFMA / dense-first-layers variant measurements")
     ap.add_argument("--overlap", action="store_true", help="run actor / weight-gradient kernels on side streams (experiment: -1 %% with the current kernels, which fill the chip; kernel timings then include contention)")
     ap.add_argument("--gru-split-bf16", type=int, default=2, choices=[0, 1, 2],
                     help="recurrent GEMMs of the GRU training scans: 2 (default) = forward scan on bf16 MFMA with operands split in three pieces (24 mantissa "
@@ -563,7 +569,7 @@ def main():
         }
         if table:
             out["kernel_table_coverage"] = round(out["kernel_table_ms_per_step"] / out["ms_per_step"], 3)
-        if world == 1 and not args.no_variants:
+        if world == 1 and args.full and not args.no_variants:
             # The same workload under the two switches that separate the headline from "plain": measured in this run, on this box, right
             # after the timed region (2 untimed + 3 timed update steps each).  fp32_mfma = exact fp32 MFMA everywhere (no bf16 x3 operand
             # splits); dense_first_layers = the first layers of both networks evaluated on every token row instead of on the distinct
@@ -596,7 +602,7 @@ def main():
                 variants["dense_first_layers_ms_per_step"] = variant(dense)
                 learner.class_tables = True
             out["variants"] = variants
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             log("timing the CPU oracle baseline ...")
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)

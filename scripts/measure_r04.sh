@@ -3,7 +3,7 @@
 # command, and the two PMC passes (FETCH_SIZE, WRITE_SIZE; separate runs) behind profiles/r04_pmc_hbm_traffic.json.
 set -o pipefail
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r04m; mkdir -p $O; cd $R
-python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err && cut -c1-420 $O/bench_default.json
+python bench.py --steps 20 --warmup 5 --full > $O/bench_default.json 2> $O/bench_default.err && cut -c1-420 $O/bench_default.json
 python bench.py --num-envs 4096 --steps 20 --warmup 3 --no-cpu-baseline --no-variants > $O/bench_4096envs.json 2> $O/bench_4096envs.err && cut -c1-330 $O/bench_4096envs.json
 python bench.py --workload coordsum-8x15 --steps 5 --warmup 2 --no-cpu-baseline --no-variants > $O/bench_8x15.json 2> $O/bench_8x15.err && cut -c1-330 $O/bench_8x15.json
 python bench.py --workload lbf-8x8-2p-2f --steps 10 --warmup 2 --no-cpu-baseline --no-variants > $O/bench_lbf.json 2> $O/bench_lbf.err && cut -c1-330 $O/bench_lbf.json

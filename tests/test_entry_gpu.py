@@ -151,6 +151,26 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel"):
         assert k in roof, k
     assert roof["bound"] in ("hbm", "mfma") and abs(roof["frac"] - roof["achieved"] / roof["peak"]) < 1e-3
+    assert "variants" not in d and "cpu_baseline" not in d   # measured with --full only
+
+
+def test_bench_full_adds_the_variant_measurements():
+    """`bench.py --full` (here without its CPU baseline leg): the same line plus the fp32-MFMA and dense-first-layers variants, each a
+    measured time per update step."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--num-envs", "256", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
+                       capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["value"] > 0 and "roofline" in d and "cpu_baseline" not in d
+    v = d["variants"]
+    assert set(v) == {"fp32_mfma_ms_per_step", "dense_first_layers_ms_per_step"}, v
+    assert all(isinstance(x, float) and x > 0 for x in v.values()), v
 
 
 def test_bench_dumps_the_outputs_of_its_last_timed_step(tmp_path):
