@@ -89,6 +89,23 @@ int magpo_rware_step(int* grid_a, int* grid_s, int* agent_pos, int* agent_dir, u
                      unsigned char* done, float* obs, long ldo, int* obs_step, unsigned char* mask, float* m_ep_ret, int* m_ep_len,
                      unsigned char* m_term, int auto_reset, magpo_stream_t stream);
 
+/* ---- VectorConnector env + wrappers (mava/wrappers/jumanji.py:223-241,346-455 VectorConnectorWrapper, AgentID, AutoReset,
+ * RecordEpisodeMetrics; the env itself is jumanji Connector-v2 with RandomWalkGenerator(grid_size, num_agents), configs/env/scenario/
+ * con-*.yaml).  UNPINNED DYNAMICS like LBF / RWARE: csrc/connector.hip and tests/connector_ref.py restate the published algorithm and
+ * agree bit for bit.  State per env: grid [G*G] (agent i: path 3i+1, position 3i+2, target 3i+3; empty 0), agent_start / agent_target /
+ * agent_pos [A][2] (row, col), step_count, key [2], metrics_key [2], episode-metric counters.  1 <= A <= 32, 2 <= G <= 16.
+ * obs rows [N][A] of ldo (>= A + 54) floats = [one-hot id | my_pos / G^2, my_target / G^2, blockers 5x5, targets 5x5]; the floats
+ * behind them are not written.  mask [N][A][5] u8 of the state after the step. */
+int magpo_connector_reset(int* grid, int* agent_start, int* agent_target, int* agent_pos, int* step_count, uint32_t* key,
+                          uint32_t* metrics_key, float* run_ret, int* run_len, float* ep_ret, int* ep_len, int N, int A,
+                          int grid_size, int time_limit, const uint32_t* env_keys, float* obs, long ldo, int* obs_step,
+                          unsigned char* mask, magpo_stream_t stream);
+int magpo_connector_step(int* grid, int* agent_start, int* agent_target, int* agent_pos, int* step_count, uint32_t* key,
+                         uint32_t* metrics_key, float* run_ret, int* run_len, float* ep_ret, int* ep_len, int N, int A,
+                         int grid_size, int time_limit, const int* actions, int act_stride, float* reward, float* discount,
+                         unsigned char* done, float* obs, long ldo, int* obs_step, unsigned char* mask, float* m_ep_ret,
+                         int* m_ep_len, unsigned char* m_term, int auto_reset, magpo_stream_t stream);
+
 /* input classes of wrapped CoordSum tokens (first-layer tables, csrc/classtab.hip): cls_enc = ((agent * maxval + target) * npos + pos),
  * cls_dec = prev * npos + pos per row; class_rows writes the distinct rows in class order: obs_tab [A*maxval*npos][A+1], pos_enc,
  * and prev_dec / pos_dec [(K+1)*npos].  The actor's class (agent, target) is cls_enc / npos (or cls_enc itself with pos = NULL, npos = 1;
@@ -190,6 +207,7 @@ int magpo_retention_chunk_bwd(const float* q, long ldq, const float* k, long ldk
                               const float* dr, long lddr, float* dq, long lddq, float* dk, long lddk, float* dv,
                               long lddv, const unsigned char* dones, const float* states, int nseq, int T, int A,
                               int masked, float kappa, int hs, const int* qkv_rows, int chunk_tokens, magpo_stream_t stream);
+/* recurrent form (acting): ntok tokens per env, 1 <= ntok <= 32 (up to 16 staged in 28 KiB of LDS, 17 - 32 in 56 KiB). */
 int magpo_retention_recurrent(float* S, const float* q, long ldq, const float* k, long ldk, const float* v, long ldv,
                               long env_stride_rows, float* r, long ldr, int nenv, int ntok, int ret_from, float decay,
                               int write_state, const float* gp, long ldg, const float* gamma, const float* beta,

@@ -549,15 +549,18 @@ __global__ __launch_bounds__(256, 1) void k_ret_chunk_bwd(RetBwdArgs a) {
 // The state is written back only when write_state != 0: the autoregressive decoder calls this once per
 // agent with the tokens decoded so far (ntok = i + 1, ret_from = i) and stores the state after the last
 // agent only, so a decoder state costs A reads + 1 write per env step instead of A reads + A writes.
-__global__ __launch_bounds__(256) void k_ret_recurrent(float* __restrict__ S, const float* __restrict__ q, const float* __restrict__ k,
-                                                       const float* __restrict__ v, long ldq, long ldk, long ldv, long env_stride_rows,
-                                                       float* __restrict__ r, long ldr, int ntok, int ret_from, float decay,
-                                                       int write_state, const float* __restrict__ gp, long ldg,
-                                                       const float* __restrict__ gamma, const float* __restrict__ beta, int hs, int gs) {
+// MAXT = tokens staged in LDS: 16 (k_ret_recurrent, every team of up to 16 agents) or 32 (k_ret_recurrent32: 56 KiB of LDS, teams of
+// 17 - 32 agents such as VectorConnector's 23).
+template <int MAXT>
+__device__ __forceinline__ void ret_recurrent_body(float* __restrict__ S, const float* __restrict__ q, const float* __restrict__ k,
+                                                   const float* __restrict__ v, long ldq, long ldk, long ldv, long env_stride_rows,
+                                                   float* __restrict__ r, long ldr, int ntok, int ret_from, float decay,
+                                                   int write_state, const float* __restrict__ gp, long ldg,
+                                                   const float* __restrict__ gamma, const float* __restrict__ beta, int hs, int gs) {
   // thread -> 4 state columns (c4..c4+3) x 4 state rows (rw, rw+16, rw+32, rw+48): float4 accesses, a wave
   // touches 4 consecutive 256-B rows (1 KiB contiguous) per instruction.
-  __shared__ __align__(16) float qs[16][64], ks[16][64], vs[16][64];
-  __shared__ __align__(16) float part[4][16][64];
+  __shared__ __align__(16) float qs[MAXT][64], ks[MAXT][64], vs[MAXT][64];
+  __shared__ __align__(16) float part[4][MAXT][64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int c4 = 4 * (tid & 15), rw = tid >> 4;
   const long env = blockIdx.x;
@@ -624,6 +627,20 @@ __global__ __launch_bounds__(256) void k_ret_recurrent(float* __restrict__ S, co
       }
     }
   }
+}
+__global__ __launch_bounds__(256) void k_ret_recurrent(float* __restrict__ S, const float* __restrict__ q, const float* __restrict__ k,
+                                                       const float* __restrict__ v, long ldq, long ldk, long ldv, long env_stride_rows,
+                                                       float* __restrict__ r, long ldr, int ntok, int ret_from, float decay,
+                                                       int write_state, const float* __restrict__ gp, long ldg,
+                                                       const float* __restrict__ gamma, const float* __restrict__ beta, int hs, int gs) {
+  ret_recurrent_body<16>(S, q, k, v, ldq, ldk, ldv, env_stride_rows, r, ldr, ntok, ret_from, decay, write_state, gp, ldg, gamma, beta, hs, gs);
+}
+__global__ __launch_bounds__(256) void k_ret_recurrent32(float* __restrict__ S, const float* __restrict__ q, const float* __restrict__ k,
+                                                         const float* __restrict__ v, long ldq, long ldk, long ldv, long env_stride_rows,
+                                                         float* __restrict__ r, long ldr, int ntok, int ret_from, float decay,
+                                                         int write_state, const float* __restrict__ gp, long ldg,
+                                                         const float* __restrict__ gamma, const float* __restrict__ beta, int hs, int gs) {
+  ret_recurrent_body<32>(S, q, k, v, ldq, ldk, ldv, env_stride_rows, r, ldr, ntok, ret_from, decay, write_state, gp, ldg, gamma, beta, hs, gs);
 }
 
 // zero the three retention states of envs whose episode just ended (rec_magpo.py:164-169)
@@ -719,10 +736,10 @@ extern "C" int magpo_retention_recurrent(float* S, const float* q, long ldq, con
                                          long env_stride_rows, float* r, long ldr, int nenv, int ntok, int ret_from, float decay,
                                          int write_state, const float* gp, long ldg, const float* gamma, const float* beta,
                                          int hs, int gs, hipStream_t st) {
-  if (ntok < 1 || ntok > 16 || ret_from < 0 || ret_from >= ntok) { set_error("retention_recurrent: 1 <= ntok <= 16, 0 <= ret_from < ntok"); return MAGPO_EINVAL; }
+  if (ntok < 1 || ntok > 32 || ret_from < 0 || ret_from >= ntok) { set_error("retention_recurrent: 1 <= ntok <= 32, 0 <= ret_from < ntok"); return MAGPO_EINVAL; }
   if (hs < 4 || hs > 64 || (hs & 3) || gs < 1 || gs > hs || (gs & (gs - 1))) { set_error("retention_recurrent: bad head width / group size"); return MAGPO_EINVAL; }
-  hipLaunchKernelGGL(k_ret_recurrent, dim3(nenv), dim3(256), 0, st, S, q, k, v, ldq, ldk, ldv, env_stride_rows, r, ldr, ntok, ret_from,
-                     decay, write_state, gp, ldg, gamma, beta, hs, gs);
+  hipLaunchKernelGGL(ntok <= 16 ? k_ret_recurrent : k_ret_recurrent32, dim3(nenv), dim3(256), 0, st, S, q, k, v, ldq, ldk, ldv, env_stride_rows, r,
+                     ldr, ntok, ret_from, decay, write_state, gp, ldg, gamma, beta, hs, gs);
   return check_launch("magpo_retention_recurrent");
 }
 

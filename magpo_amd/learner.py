@@ -231,6 +231,51 @@ class RwareEnvBatch:
                     m_term, 1 if auto_reset else 0, torch.cuda.current_stream().cuda_stream)
 
 
+@dataclass
+class VectorConnectorConfig:
+    """jumanji Connector-v2 + RandomWalkGenerator(**task_config) (configs/env/scenario/con-*.yaml) under VectorConnectorWrapper."""
+    grid_size: int = 10
+    num_agents: int = 10
+    time_limit: int = 100
+    has_mask = True
+    class_tables = False
+    num_actions = 5
+
+    @property
+    def obs_dim(self) -> int:   # 4 coordinates + two 5 x 5 windows + one-hot agent id
+        return 54 + self.num_agents
+
+
+class ConnectorEnvBatch:
+    """Device-resident batch of wrapped VectorConnector envs (csrc/connector.hip; UNPINNED dynamics, see its header comment)."""
+    state_fields = ("grid", "agent_start", "agent_target", "agent_pos", "step_count", "key", "metrics_key", "run_ret", "run_len", "ep_ret",
+                    "ep_len")
+
+    def __init__(self, cfg: VectorConnectorConfig, N: int, device):
+        self.cfg, self.N, self.dev = cfg, N, device
+        self.L = lib()
+        A, G = cfg.num_agents, cfg.grid_size
+        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
+        self.grid = i32(N, G, G)
+        self.agent_start, self.agent_target, self.agent_pos = i32(N, A, 2), i32(N, A, 2), i32(N, A, 2)
+        self.step_count, self.key, self.metrics_key = i32(N), i32(N, 2), i32(N, 2)
+        self.run_ret, self.run_len = torch.zeros(N, device=device), i32(N)
+        self.ep_ret, self.ep_len = torch.zeros(N, device=device), i32(N)
+        self.ldo = obs_row_stride(cfg.obs_dim)
+
+    def _args(self):
+        c = self.cfg
+        return (self.grid, self.agent_start, self.agent_target, self.agent_pos, self.step_count, self.key, self.metrics_key, self.run_ret,
+                self.run_len, self.ep_ret, self.ep_len, self.N, c.num_agents, c.grid_size, c.time_limit)
+
+    def reset(self, env_keys: torch.Tensor, obs, obs_step, mask=None):
+        self.L.call("magpo_connector_reset", *self._args(), env_keys, obs, self.ldo, obs_step, mask, torch.cuda.current_stream().cuda_stream)
+
+    def step(self, actions, reward, done, obs, obs_step, m_ret, m_len, m_term, auto_reset=True, mask=None, discount=None):
+        self.L.call("magpo_connector_step", *self._args(), actions, self.cfg.num_agents, reward, discount, done, obs, self.ldo, obs_step, mask,
+                    m_ret, m_len, m_term, 1 if auto_reset else 0, torch.cuda.current_stream().cuda_stream)
+
+
 def obs_row_stride(obs_dim: int) -> int:
     """Floats between observation rows: obs_dim for small observations, 128 (zero-padded) for wide ones (csrc/wideobs.hip)."""
     return obs_dim if obs_dim <= 32 else 128
@@ -239,6 +284,8 @@ def obs_row_stride(obs_dim: int) -> int:
 def make_env_batch(cfg, N: int, device):
     if isinstance(cfg, RwareConfig):
         return RwareEnvBatch(cfg, N, device)
+    if isinstance(cfg, VectorConnectorConfig):
+        return ConnectorEnvBatch(cfg, N, device)
     return LbfEnvBatch(cfg, N, device) if isinstance(cfg, LbfConfig) else CoordSumEnvBatch(cfg, N, device)
 
 

@@ -462,8 +462,6 @@ class SableGuider:
         ``defer`` / ``precand`` (include/magpo.h): inside a rollout half of the workgroups run the block-0 candidate pre-pass of the NEXT
         step at the end of the launch (defer) and skip it in the next one (precand), so that they stream states while the others decode."""
         A, K, F, nb, nh = self.A, self.K, self.F, self.nb, self.nh
-        if A > 8 and self.wide:
-            raise NotImplementedError("wide observations (obs_dim > 32) with more than 8 agents")
         if A > 8 or self.E != 64:   # token staging registers / 64-wide register rows of the fused kernel: larger teams take the kernel-by-kernel path (states settled on return)
             if done is not None:
                 for k in range(nb):

@@ -1,8 +1,9 @@
 """Environment factory (mava/utils/make_env.py:202-218, 288-315): config -> (train_env, eval_env) descriptors.
 
-CoordSum (csrc/coordsum.hip), Level-Based Foraging (csrc/lbf.hip) and Robot Warehouse (csrc/rware.hip) are implemented.  LBF / RWARE
-dynamics live in third-party Jumanji, which is absent from the reference tree and from this image: both are restated from
-Jumanji's published algorithm with UNPINNED dynamics (oracle/lbf.py and oracle/rware.py list every rule).
+CoordSum (csrc/coordsum.hip), Level-Based Foraging (csrc/lbf.hip), Robot Warehouse (csrc/rware.hip) and VectorConnector
+(csrc/connector.hip) are implemented.  LBF / RWARE / Connector dynamics live in third-party Jumanji, which is absent from the reference
+tree and from this image: all three are restated from Jumanji's published algorithm with UNPINNED dynamics (oracle/lbf.py,
+oracle/rware.py and tests/connector_ref.py list every rule).  The grid-observation ``Connector`` (ConnectorWrapper) is not supported.
 """
 from __future__ import annotations
 
@@ -13,7 +14,7 @@ import numpy as np
 import torch
 
 from .. import specs
-from ..learner import CoordSumConfig, LbfConfig, RwareConfig, make_env_batch, obs_row_stride
+from ..learner import CoordSumConfig, LbfConfig, RwareConfig, VectorConnectorConfig, make_env_batch, obs_row_stride
 from ..types import Observation, TimeStep
 
 COORDSUM_REGISTRY = {  # mava/coordsum/__init__.py:6-45
@@ -48,7 +49,7 @@ class MarlEnv:
     """The env API the system file, the learner set-up and the evaluator use (mava/types.py:45-123 ``MarlEnv``): ``num_agents`` /
     ``time_limit`` / ``action_dim``, ``reset(key) -> (state, timestep)``, ``step(state, action) -> (state, timestep)``,
     ``observation_spec`` / ``action_spec`` / ``reward_spec`` / ``discount_spec`` and ``unwrapped`` -- driving the HIP env kernels
-    (csrc/coordsum.hip, lbf.hip, rware.hip), which implement the whole wrapper stack of mava/utils/make_env.py:90-104
+    (csrc/coordsum.hip, lbf.hip, rware.hip, connector.hip), which implement the whole wrapper stack of mava/utils/make_env.py:90-104
     (env wrapper -> AgentIDWrapper -> AutoResetWrapper [train env] -> RecordEpisodeMetrics).
 
     The batch axis is explicit: the reference calls ``jax.vmap(env.reset)(keys)`` / ``jax.vmap(env.step)(state, action)``; here
@@ -217,6 +218,27 @@ def make_rware_env(config):
     return MarlEnvSpec(cfg, auto_reset=True), MarlEnvSpec(cfg, auto_reset=False)
 
 
+def make_vector_connector_env(config):
+    """make_jumanji_env (make_env.py:107-135) for VectorConnector (_jumanji_registry, make_env.py:64-75): generator =
+    RandomWalkGenerator(**scenario.task_config), env kwargs = {**env.kwargs, **scenario.env_kwargs} (time_limit only), wrapped by
+    VectorConnectorWrapper with its default aggregate_rewards (the factory never passes env.aggregate_rewards, as for LBF)."""
+    tc = config.env.scenario.task_config.to_container()
+    kw = {**config.env.kwargs.to_container(), **config.env.scenario.env_kwargs.to_container()}
+    unknown = set(kw) - {"time_limit"}
+    if unknown:
+        raise NotImplementedError(f"VectorConnector kwargs {sorted(unknown)} are not supported")
+    add_id = bool(config.system.add_agent_id) and not bool(config.env.implicit_agent_id)
+    config.system.add_agent_id = add_id
+    if not add_id:
+        raise NotImplementedError("system.add_agent_id=False with VectorConnector: its 128-float padded observation rows are read with 16-byte "
+                                  "vector loads that the column offset behind the one-hot id would misalign (CoordSum and LBF support it)")
+    cfg = VectorConnectorConfig(grid_size=int(tc["grid_size"]), num_agents=int(tc["num_agents"]), time_limit=int(kw.get("time_limit", 100)))
+    G, A = cfg.grid_size, cfg.num_agents
+    if not (2 <= G <= 16 and 1 <= A <= 32 and A <= G * G):
+        raise NotImplementedError("VectorConnector: 2 <= grid_size <= 16 and 1 <= num_agents <= min(32, grid_size^2) (csrc/connector.hip)")
+    return MarlEnvSpec(cfg, auto_reset=True), MarlEnvSpec(cfg, auto_reset=False)
+
+
 def make(config):
     env_name = config.env.env_name
     if env_name == "CoordSum":
@@ -225,4 +247,6 @@ def make(config):
         return make_lbf_env(config)
     if env_name == "RobotWarehouse":
         return make_rware_env(config)
+    if env_name == "VectorConnector":
+        return make_vector_connector_env(config)
     raise ValueError(f"{env_name} is not a supported environment.")
