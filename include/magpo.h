@@ -106,6 +106,21 @@ int magpo_connector_step(int* grid, int* agent_start, int* agent_target, int* ag
                          unsigned char* done, float* obs, long ldo, int* obs_step, unsigned char* mask, float* m_ep_ret,
                          int* m_ep_len, unsigned char* m_term, int auto_reset, magpo_stream_t stream);
 
+/* ---- MPE simple_spread env, discrete actions, + wrappers (mava/wrappers/jaxmarl.py:169-243,424-455 MPEWrapper, AgentID, AutoReset,
+ * RecordEpisodeMetrics; the env itself is JaxMARL MPE_simple_spread_v3(num_agents, num_landmarks, local_ratio), configs/env/scenario/
+ * simple_spread_*.yaml).  UNPINNED DYNAMICS: csrc/mpe.hip and tests/mpe_ref.py restate the published algorithm and agree bit for bit.
+ * State per env: pos [A+L][2] f32 (agents, then landmarks), vel [A][2] f32, inner_step (the env's counter), step_count (the wrapper's
+ * counter), key [2], metrics_key [2], episode-metric counters.  1 <= A <= 32, 1 <= L <= 32.  obs rows [N][A] of ldo (>= 5 A + 2 L)
+ * floats = [one-hot id | vel, pos, landmarks - pos, other agents - pos, comm (zeros)]; the floats behind them are not written.  Every
+ * action is legal: no mask.  reward [N][A] per agent; an episode lasts time_limit + 1 steps. */
+int magpo_mpe_reset(float* pos, float* vel, int* inner_step, int* step_count, uint32_t* key, uint32_t* metrics_key, float* run_ret,
+                    int* run_len, float* ep_ret, int* ep_len, int N, int A, int L, int time_limit, float local_ratio,
+                    const uint32_t* env_keys, float* obs, long ldo, int* obs_step, magpo_stream_t stream);
+int magpo_mpe_step(float* pos, float* vel, int* inner_step, int* step_count, uint32_t* key, uint32_t* metrics_key, float* run_ret,
+                   int* run_len, float* ep_ret, int* ep_len, int N, int A, int L, int time_limit, float local_ratio, const int* actions,
+                   int act_stride, float* reward, float* discount, unsigned char* done, float* obs, long ldo, int* obs_step,
+                   float* m_ep_ret, int* m_ep_len, unsigned char* m_term, int auto_reset, magpo_stream_t stream);
+
 /* input classes of wrapped CoordSum tokens (first-layer tables, csrc/classtab.hip): cls_enc = ((agent * maxval + target) * npos + pos),
  * cls_dec = prev * npos + pos per row; class_rows writes the distinct rows in class order: obs_tab [A*maxval*npos][A+1], pos_enc,
  * and prev_dec / pos_dec [(K+1)*npos].  The actor's class (agent, target) is cls_enc / npos (or cls_enc itself with pos = NULL, npos = 1;

@@ -276,6 +276,51 @@ class ConnectorEnvBatch:
                     m_ret, m_len, m_term, 1 if auto_reset else 0, torch.cuda.current_stream().cuda_stream)
 
 
+@dataclass
+class MpeConfig:
+    """JaxMARL MPE_simple_spread_v3(**task_config) (configs/env/scenario/simple_spread_*.yaml), discrete actions, under MPEWrapper."""
+    num_agents: int = 3
+    num_landmarks: int = 3
+    local_ratio: float = 0.5
+    time_limit: int = 25        # SimpleMPE max_steps; an episode lasts time_limit + 1 steps (csrc/mpe.hip)
+    add_agent_id: bool = True   # system.add_agent_id: False = the networks read the rows behind the one-hot id (narrow rows only, net_obs)
+    has_mask = False            # every action is legal (MPEWrapper.action_mask): never stored
+    class_tables = False
+    num_actions = 5
+
+    @property
+    def obs_dim(self) -> int:   # vel, pos, landmarks, other agents' positions and (silent) comm + one-hot agent id
+        return 4 + 2 * self.num_landmarks + 4 * (self.num_agents - 1) + self.num_agents
+
+
+class MpeEnvBatch:
+    """Device-resident batch of wrapped MPE simple_spread envs (csrc/mpe.hip; UNPINNED dynamics, see tests/mpe_ref.py)."""
+    state_fields = ("pos", "vel", "inner_step", "step_count", "key", "metrics_key", "run_ret", "run_len", "ep_ret", "ep_len")
+
+    def __init__(self, cfg: MpeConfig, N: int, device):
+        self.cfg, self.N, self.dev = cfg, N, device
+        self.L = lib()
+        A, L = cfg.num_agents, cfg.num_landmarks
+        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
+        self.pos, self.vel = torch.zeros(N, A + L, 2, device=device), torch.zeros(N, A, 2, device=device)
+        self.inner_step, self.step_count, self.key, self.metrics_key = i32(N), i32(N), i32(N, 2), i32(N, 2)
+        self.run_ret, self.run_len = torch.zeros(N, device=device), i32(N)
+        self.ep_ret, self.ep_len = torch.zeros(N, device=device), i32(N)
+        self.ldo = obs_row_stride(cfg.obs_dim)
+
+    def _args(self):
+        c = self.cfg
+        return (self.pos, self.vel, self.inner_step, self.step_count, self.key, self.metrics_key, self.run_ret, self.run_len, self.ep_ret,
+                self.ep_len, self.N, c.num_agents, c.num_landmarks, c.time_limit, float(c.local_ratio))
+
+    def reset(self, env_keys: torch.Tensor, obs, obs_step, mask=None):
+        self.L.call("magpo_mpe_reset", *self._args(), env_keys, obs, self.ldo, obs_step, torch.cuda.current_stream().cuda_stream)
+
+    def step(self, actions, reward, done, obs, obs_step, m_ret, m_len, m_term, auto_reset=True, mask=None, discount=None):
+        self.L.call("magpo_mpe_step", *self._args(), actions, self.cfg.num_agents, reward, discount, done, obs, self.ldo, obs_step, m_ret, m_len,
+                    m_term, 1 if auto_reset else 0, torch.cuda.current_stream().cuda_stream)
+
+
 def obs_row_stride(obs_dim: int) -> int:
     """Floats between observation rows: obs_dim for small observations, 128 (zero-padded) for wide ones (csrc/wideobs.hip)."""
     return obs_dim if obs_dim <= 32 else 128
@@ -286,6 +331,8 @@ def make_env_batch(cfg, N: int, device):
         return RwareEnvBatch(cfg, N, device)
     if isinstance(cfg, VectorConnectorConfig):
         return ConnectorEnvBatch(cfg, N, device)
+    if isinstance(cfg, MpeConfig):
+        return MpeEnvBatch(cfg, N, device)
     return LbfEnvBatch(cfg, N, device) if isinstance(cfg, LbfConfig) else CoordSumEnvBatch(cfg, N, device)
 
 

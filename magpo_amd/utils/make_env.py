@@ -1,9 +1,10 @@
 """Environment factory (mava/utils/make_env.py:202-218, 288-315): config -> (train_env, eval_env) descriptors.
 
-CoordSum (csrc/coordsum.hip), Level-Based Foraging (csrc/lbf.hip), Robot Warehouse (csrc/rware.hip) and VectorConnector
-(csrc/connector.hip) are implemented.  LBF / RWARE / Connector dynamics live in third-party Jumanji, which is absent from the reference
-tree and from this image: all three are restated from Jumanji's published algorithm with UNPINNED dynamics (oracle/lbf.py,
-oracle/rware.py and tests/connector_ref.py list every rule).  The grid-observation ``Connector`` (ConnectorWrapper) is not supported.
+CoordSum (csrc/coordsum.hip), Level-Based Foraging (csrc/lbf.hip), Robot Warehouse (csrc/rware.hip), VectorConnector
+(csrc/connector.hip) and MPE simple_spread with discrete actions (csrc/mpe.hip) are implemented.  LBF / RWARE / Connector dynamics live in
+third-party Jumanji and MPE's in JaxMARL, both absent from the reference tree and from this image: all four are restated from the published
+algorithms with UNPINNED dynamics (oracle/lbf.py, oracle/rware.py, tests/connector_ref.py and tests/mpe_ref.py list every rule).  The
+grid-observation ``Connector`` (ConnectorWrapper) and MPE's continuous actions are not supported.
 """
 from __future__ import annotations
 
@@ -14,7 +15,7 @@ import numpy as np
 import torch
 
 from .. import specs
-from ..learner import CoordSumConfig, LbfConfig, RwareConfig, VectorConnectorConfig, make_env_batch, obs_row_stride
+from ..learner import CoordSumConfig, LbfConfig, MpeConfig, RwareConfig, VectorConnectorConfig, make_env_batch, net_obs, obs_row_stride
 from ..types import Observation, TimeStep
 
 COORDSUM_REGISTRY = {  # mava/coordsum/__init__.py:6-45
@@ -239,6 +240,31 @@ def make_vector_connector_env(config):
     return MarlEnvSpec(cfg, auto_reset=True), MarlEnvSpec(cfg, auto_reset=False)
 
 
+def make_mpe_env(config):
+    """make_jaxmarl_env (make_env.py:138-170) for MPE: kwargs = {**env.kwargs, **scenario.task_config} for
+    jaxmarl.make(scenario.name, **kwargs), wrapped by MPEWrapper (time_limit = the env's max_steps).  Discrete actions only."""
+    kw = {**config.env.kwargs.to_container(), **config.env.scenario.task_config.to_container()}
+    unknown = set(kw) - {"action_type", "num_agents", "num_landmarks", "local_ratio", "max_steps"}
+    if unknown:
+        raise NotImplementedError(f"MPE kwargs {sorted(unknown)} are not supported")
+    action_type = kw.get("action_type", "Discrete")
+    if action_type == "Continuous":
+        raise NotImplementedError("MPE with continuous actions (tanh-Gaussian heads) is not supported: override env.kwargs.action_type=Discrete")
+    if action_type != "Discrete":
+        raise ValueError(f"MPE action_type {action_type!r}: 'Discrete' or 'Continuous'")
+    add_id = bool(config.system.add_agent_id) and not bool(config.env.implicit_agent_id)
+    config.system.add_agent_id = add_id
+    cfg = MpeConfig(num_agents=int(kw.get("num_agents", 3)), num_landmarks=int(kw.get("num_landmarks", 3)),
+                    local_ratio=float(kw.get("local_ratio", 0.5)), time_limit=int(kw.get("max_steps", 25)), add_agent_id=add_id)
+    A, L = cfg.num_agents, cfg.num_landmarks
+    if not (1 <= A <= 32 and 1 <= L <= 32 and cfg.time_limit >= 1):
+        raise ValueError("MPE: 1 <= num_agents <= 32, 1 <= num_landmarks <= 32 and max_steps >= 1 (csrc/mpe.hip)")
+    if cfg.obs_dim > 128:
+        raise NotImplementedError(f"MPE: observations of {cfg.obs_dim} floats (5 num_agents + 2 num_landmarks <= 128 required)")
+    net_obs(cfg)   # system.add_agent_id=False needs narrow rows (3 agents: 18 features)
+    return MarlEnvSpec(cfg, auto_reset=True, add_agent_id=add_id), MarlEnvSpec(cfg, auto_reset=False, add_agent_id=add_id)
+
+
 def make(config):
     env_name = config.env.env_name
     if env_name == "CoordSum":
@@ -249,4 +275,6 @@ def make(config):
         return make_rware_env(config)
     if env_name == "VectorConnector":
         return make_vector_connector_env(config)
+    if env_name == "MPE":
+        return make_mpe_env(config)
     raise ValueError(f"{env_name} is not a supported environment.")
