@@ -1,4 +1,8 @@
-"""GPU parity of every primitive HIP kernel against the CPU oracle / torch fp64 (through the C ABI)."""
+"""GPU parity of the primitive HIP kernels against the CPU oracle / torch fp64 (through the C ABI): dense layers and weight gradients,
+the embedding / norm / head row kernels, chunkwise retention, the GRU scans, sampling, PRNG, the CoordSum env, GAE, losses, optimiser,
+minibatch gather and class sums.  The fused segments are in test_segment_kernels_gpu.py, the kernel-by-kernel acting primitives in
+test_act_primitives_gpu.py, the wide-observation / small-first-layer / class-id / helper kernels in test_row_kernels_gpu.py;
+test_abi_coverage.py (CPU) checks that every entry point of include/magpo.h is named by one of the GPU modules."""
 import math
 
 import numpy as np
