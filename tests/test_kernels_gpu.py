@@ -2,6 +2,7 @@
 the embedding / norm / head row kernels, chunkwise retention, the GRU scans, sampling, PRNG, the CoordSum env, GAE, losses, optimiser,
 minibatch gather and class sums.  The fused segments are in test_segment_kernels_gpu.py, the kernel-by-kernel acting primitives in
 test_act_primitives_gpu.py, the wide-observation / small-first-layer / class-id / helper kernels in test_row_kernels_gpu.py;
+the RL-side kernels again at production strides, edge shapes and loss kinks, with guarded outputs, in test_rl_kernels_gpu.py;
 test_abi_coverage.py (CPU) checks that every entry point of include/magpo.h is named by one of the GPU modules."""
 import math
 
