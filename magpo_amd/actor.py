@@ -37,7 +37,7 @@ class GruActor:
         self.A, self.K, self.F = n_agents, action_dim, obs_dim
         self.wide = obs_dim > 32            # wide observations: rows padded to 128, pre-torso on the MFMA dense kernel (csrc/wideobs.hip)
         self.Fld = 128 if self.wide else obs_dim      # floats between observation rows
-        if obs_ld is not None and int(obs_ld) != self.Fld:   # rows wider than the features read (system.add_agent_id: False, learner.net_obs)
+        if obs_ld is not None and int(obs_ld) != self.Fld:   # rows wider than the features read (system.add_agent_id: False, envs.net_obs)
             if self.wide or int(obs_ld) < obs_dim:
                 raise ValueError(f"obs_ld={obs_ld} with obs_dim={obs_dim}: a separate row stride is supported for narrow observations only")
             self.Fld = int(obs_ld)

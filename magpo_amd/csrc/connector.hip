@@ -20,7 +20,7 @@
 //     connected: its target value owns the cell).
 // One thread per env working in place on the env's grid in HBM ([N][G*G] int32, G <= 16).  A step reads a few cells per agent and
 // the two 5 x 5 windows of every agent's view: a small latency-bound stream next to the acting kernel.
-#include "common.hpp"
+#include "env_wrappers.hpp"
 
 namespace magpo {
 
@@ -32,8 +32,8 @@ struct CnState {
   int* grid;                          // [N][G*G]
   int* start; int* target; int* pos;  // [N][A][2] (row, col)
   int* step_count;                    // [N]
-  uint32_t* key; uint32_t* metrics_key;   // [N][2]
-  float* run_ret; int* run_len; float* ep_ret; int* ep_len;
+  uint32_t* key;                      // [N][2]
+  EpisodeMetrics m;
 };
 struct CnCfg { int N, A, G, TLIM; };
 
@@ -84,10 +84,8 @@ __device__ void cn_generate(const CnCfg& c, const CnState& s, long n, uint32_t k
   int* g = s.grid + n * GG;
   int* pos = s.pos + n * A * 2;
   uint32_t ks0, ks1, b0, b1, st0, st1, kk0, kk1;
-  threefry2x32(k0, k1, 0u, 0u, ks0, ks1);   // key (kept by the state), board_key = split(key)
-  threefry2x32(k0, k1, 0u, 1u, b0, b1);
-  threefry2x32(b0, b1, 0u, 0u, kk0, kk1);   // key, step_key = split(board_key)
-  threefry2x32(b0, b1, 0u, 1u, st0, st1);
+  split_key(k0, k1, ks0, ks1, b0, b1);      // key (kept by the state), board_key = split(key)
+  split_key(b0, b1, kk0, kk1, st0, st1);    // key, step_key = split(board_key)
   for (int i = 0; i < GG; ++i) g[i] = 0;
   int starts[CN_MAXA], cand[CN_MAXA];
   cn_perm_prefix(kk0, kk1, GG, A, starts);
@@ -110,8 +108,7 @@ __device__ void cn_generate(const CnCfg& c, const CnState& s, long n, uint32_t k
     }
     if (!any) break;
     uint32_t c0, c1, n0, n1;
-    threefry2x32(st0, st1, 0u, 0u, c0, c1);   // cur, step_key = split(step_key)
-    threefry2x32(st0, st1, 0u, 1u, n0, n1);
+    split_key(st0, st1, c0, c1, n0, n1);   // cur, step_key = split(step_key)
     st0 = n0; st1 = n1;
     for (int a = 0; a < A; ++a) {
       uint32_t a0, a1;
@@ -189,27 +186,18 @@ __device__ bool cn_observe(const CnCfg& c, const CnState& s, long n, float* __re
 
 __global__ __launch_bounds__(64) void k_connector_reset(CnState s, CnCfg c, const uint32_t* __restrict__ env_keys, float* __restrict__ obs, long ldo,
                                                         int* __restrict__ obs_step, unsigned char* __restrict__ mask) {
-  const long n = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= c.N) return;
-  const uint32_t e0 = env_keys[2 * n], e1 = env_keys[2 * n + 1];
-  uint32_t m0, m1, r0, r1;
-  threefry2x32(e0, e1, 0u, 0u, m0, m1);  // key, reset_key = split(key)   (episode_metrics.py:62)
-  threefry2x32(e0, e1, 0u, 1u, r0, r1);
+  long n;
+  if (!env_index(c.N, n)) return;
+  uint32_t r0, r1;
+  metrics_reset(s.m, n, env_keys[2 * n], env_keys[2 * n + 1], r0, r1);
   cn_generate(c, s, n, r0, r1);
-  s.metrics_key[2 * n] = m0; s.metrics_key[2 * n + 1] = m1;
-  s.run_ret[n] = 0.f; s.run_len[n] = 0; s.ep_ret[n] = 0.f; s.ep_len[n] = 0;
   cn_observe(c, s, n, obs + n * (long)c.A * ldo, ldo, mask + n * (long)c.A * CN_NACT);
   obs_step[n] = 0;
 }
 
-struct CnOut {
-  float* reward; float* discount; unsigned char* done; float* obs; long ldo; int* obs_step; unsigned char* mask;
-  float* m_ep_ret; int* m_ep_len; unsigned char* m_term;
-};
-
-__global__ __launch_bounds__(64) void k_connector_step(CnState s, CnCfg c, const int* __restrict__ actions, int act_stride, CnOut o, int auto_reset) {
-  const long n = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= c.N) return;
+__global__ __launch_bounds__(64) void k_connector_step(CnState s, CnCfg c, const int* __restrict__ actions, int act_stride, StepOut o, int auto_reset) {
+  long n;
+  if (!env_index(c.N, n)) return;
   const int A = c.A, G = c.G;
   int* g = s.grid + n * G * G;
   int* pos = s.pos + n * A * 2; const int* target = s.target + n * A * 2;
@@ -241,28 +229,14 @@ __global__ __launch_bounds__(64) void k_connector_step(CnState s, CnCfg c, const
   int obs_step = steps;
   if (done && auto_reset) {
     uint32_t nk0, nk1;
-    threefry2x32(s.key[2 * n], s.key[2 * n + 1], 0u, 0u, nk0, nk1);  // key, _ = split(state.key)   (auto_reset_wrapper.py:74)
+    split_key_first(s.key[2 * n], s.key[2 * n + 1], nk0, nk1);
     cn_generate(c, s, n, nk0, nk1);
     cn_observe(c, s, n, ob, o.ldo, mk);
     obs_step = 0;
   }
   o.obs_step[n] = obs_step;
-  for (int a = 0; a < A; ++a) o.reward[n * A + a] = reward;
-  if (o.discount) for (int a = 0; a < A; ++a) o.discount[n * A + a] = done ? 0.f : 1.f;   // all connected / blocked or horizon: termination
-  o.done[n] = done ? 1 : 0;
-  float msum = 0.f;   // episode_metrics.py:79-112: mean over agents of the repeated reward, as a sum / A in fp32
-  for (int a = 0; a < A; ++a) msum += reward;
-  const float new_ret = s.run_ret[n] + __fdiv_rn(msum, (float)A);
-  const int new_len = s.run_len[n] + 1;
-  const float ep_ret = done ? new_ret : s.ep_ret[n];
-  const int ep_len = done ? new_len : s.ep_len[n];
-  s.run_ret[n] = done ? 0.f : new_ret;
-  s.run_len[n] = done ? 0 : new_len;
-  s.ep_ret[n] = ep_ret;
-  s.ep_len[n] = ep_len;
-  o.m_ep_ret[n] = ep_ret;
-  o.m_ep_len[n] = ep_len;
-  o.m_term[n] = done ? 1 : 0;
+  write_team_outputs(o, n, A, reward, done, done);   // all connected / blocked or horizon: termination
+  metrics_step(s.m, o, n, team_mean(reward, A), done);
 }
 
 }  // namespace magpo
@@ -285,9 +259,9 @@ extern "C" int magpo_connector_reset(int* grid, int* agent_start, int* agent_tar
                                      hipStream_t st) {
   CnCfg c;
   if (int e = cn_cfg(c, N, A, grid_size, time_limit, ldo)) return e;
-  if (N <= 0) return MAGPO_OK;
-  CnState s{grid, agent_start, agent_target, agent_pos, step_count, key, metrics_key, run_ret, run_len, ep_ret, ep_len};
-  hipLaunchKernelGGL(k_connector_reset, dim3((N + 63) / 64), dim3(64), 0, st, s, c, env_keys, obs, ldo, obs_step, mask);
+  if (int e = env_args(N); e != ENV_LAUNCH) return e;
+  CnState s{grid, agent_start, agent_target, agent_pos, step_count, key, {metrics_key, run_ret, run_len, ep_ret, ep_len}};
+  hipLaunchKernelGGL(k_connector_reset, env_grid(N), dim3(ENV_BLOCK), 0, st, s, c, env_keys, obs, ldo, obs_step, mask);
   return check_launch("magpo_connector_reset");
 }
 
@@ -298,10 +272,9 @@ extern "C" int magpo_connector_step(int* grid, int* agent_start, int* agent_targ
                                     unsigned char* m_term, int auto_reset, hipStream_t st) {
   CnCfg c;
   if (int e = cn_cfg(c, N, A, grid_size, time_limit, ldo)) return e;
-  if (N <= 0) return MAGPO_OK;
-  if (act_stride < A) { set_error("connector: act_stride < num_agents"); return MAGPO_EINVAL; }
-  CnState s{grid, agent_start, agent_target, agent_pos, step_count, key, metrics_key, run_ret, run_len, ep_ret, ep_len};
-  CnOut o{reward, discount, done, obs, ldo, obs_step, mask, m_ep_ret, m_ep_len, m_term};
-  hipLaunchKernelGGL(k_connector_step, dim3((N + 63) / 64), dim3(64), 0, st, s, c, actions, act_stride, o, auto_reset);
+  if (int e = env_args(N, A, act_stride, "connector: act_stride < num_agents"); e != ENV_LAUNCH) return e;
+  CnState s{grid, agent_start, agent_target, agent_pos, step_count, key, {metrics_key, run_ret, run_len, ep_ret, ep_len}};
+  StepOut o{reward, discount, done, obs, ldo, obs_step, mask, m_ep_ret, m_ep_len, m_term};
+  hipLaunchKernelGGL(k_connector_step, env_grid(N), dim3(ENV_BLOCK), 0, st, s, c, actions, act_stride, o, auto_reset);
   return check_launch("magpo_connector_step");
 }

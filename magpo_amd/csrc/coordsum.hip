@@ -8,7 +8,7 @@
 // per-action histogram is K wave ballots; JAX's clamped out-of-range gather / dynamic_update_slice
 // (record row min(target, K-1)) is reproduced explicitly.  Auto-reset branches per env
 // (the reference evaluates reset for every env every step under vmap(cond)).
-#include "common.hpp"
+#include "env_wrappers.hpp"
 
 namespace magpo {
 
@@ -17,8 +17,7 @@ struct CoordSumState {
   int* target;           // [N][TLIM+1]
   int* record;           // [N][K][TLIM]
   uint32_t* key;         // [N][2]   CoordSum State.key
-  uint32_t* metrics_key; // [N][2]   RecordEpisodeMetricsState.key (kept, never consumed)
-  float* run_ret; int* run_len; float* ep_ret; int* ep_len;  // [N] episode metric counters
+  EpisodeMetrics m;
 };
 struct CoordSumCfg { int N, A, K, TLIM, maxval; };
 
@@ -32,12 +31,9 @@ __device__ __forceinline__ int randint_elem(uint32_t ka0, uint32_t ka1, uint32_t
 
 // CoordSum.reset for one env by one wave: fills target / record / step_count / key; returns target[0] on lane 0.
 __device__ __forceinline__ int core_reset(const CoordSumState& s, const CoordSumCfg& c, long n, uint32_t k0, uint32_t k1, int lane) {
-  uint32_t nk0, nk1, t0, t1;
-  threefry2x32(k0, k1, 0u, 0u, nk0, nk1);   // key
-  threefry2x32(k0, k1, 0u, 1u, t0, t1);     // target_key
-  uint32_t a0, a1, b0, b1;
-  threefry2x32(t0, t1, 0u, 0u, a0, a1);     // randint: k1, k2 = split(target_key)
-  threefry2x32(t0, t1, 0u, 1u, b0, b1);
+  uint32_t nk0, nk1, t0, t1, a0, a1, b0, b1;
+  split_key(k0, k1, nk0, nk1, t0, t1);   // key, target_key
+  split_key(t0, t1, a0, a1, b0, b1);     // randint: k1, k2 = split(target_key)
   const uint32_t span = c.maxval > 0 ? (uint32_t)c.maxval : 1u;
   int first = 0;
   for (int i = lane; i <= c.TLIM; i += 64) {
@@ -71,26 +67,11 @@ __global__ __launch_bounds__(256) void k_coordsum_reset(CoordSumState s, CoordSu
   const int lane = threadIdx.x & 63;
   const long n = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (n >= c.N) return;
-  const uint32_t e0 = env_keys[2 * n], e1 = env_keys[2 * n + 1];
-  uint32_t m0, m1, r0, r1;
-  threefry2x32(e0, e1, 0u, 0u, m0, m1);  // key, reset_key = split(key)   (episode_metrics.py:62)
-  threefry2x32(e0, e1, 0u, 1u, r0, r1);
+  uint32_t r0, r1;
+  metrics_reset(s.m, n, env_keys[2 * n], env_keys[2 * n + 1], r0, r1, lane == 0);
   const int tv = core_reset(s, c, n, r0, r1, lane);
-  if (lane == 0) {
-    s.metrics_key[2 * n] = m0; s.metrics_key[2 * n + 1] = m1;
-    s.run_ret[n] = 0.f; s.run_len[n] = 0; s.ep_ret[n] = 0.f; s.ep_len[n] = 0;
-  }
   write_obs(obs, obs_step, n, c, tv, 0, lane);
 }
-
-struct StepOut {
-  float* reward;          // [N][A]
-  float* discount;        // [N][A] or NULL: 0 on termination (done), 1 otherwise (timestep.discount)
-  unsigned char* done;    // [N]   timestep.last()
-  float* obs;             // [N][A][A+1]  next observation (reset obs after auto-reset)
-  int* obs_step;          // [N]          observation.step_count
-  float* m_ep_ret; int* m_ep_len; unsigned char* m_term;  // [N] extras["episode_metrics"]
-};
 
 __global__ __launch_bounds__(256) void k_coordsum_step(CoordSumState s, CoordSumCfg c, const int* __restrict__ actions,
                                                        int act_stride, StepOut o, int auto_reset) {
@@ -132,28 +113,13 @@ __global__ __launch_bounds__(256) void k_coordsum_step(CoordSumState s, CoordSum
   if (lane == 0) s.step_count[n] = steps;
   if (done && auto_reset) {
     uint32_t k0 = s.key[2 * n], k1 = s.key[2 * n + 1], nk0, nk1;
-    threefry2x32(k0, k1, 0u, 0u, nk0, nk1);  // key, _ = split(state.key)   (auto_reset_wrapper.py:74)
+    split_key_first(k0, k1, nk0, nk1);
     obs_target = core_reset(s, c, n, nk0, nk1, lane);
     obs_step = 0;
   }
-  for (int a = lane; a < c.A; a += 64) o.reward[n * c.A + a] = reward;
-  if (o.discount) for (int a = lane; a < c.A; a += 64) o.discount[n * c.A + a] = done ? 0.f : 1.f;   // termination() at the time limit (coordsum/env.py:121-129)
+  write_team_outputs(o, n, c.A, reward, done, done, lane, 64);   // termination() at the time limit (coordsum/env.py:121-129)
   write_obs(o.obs, o.obs_step, n, c, obs_target, obs_step, lane);
-  if (lane == 0) {
-    o.done[n] = done ? 1 : 0;
-    // episode_metrics.py:79-112 (mean over agents of identical rewards == reward)
-    const float new_ret = s.run_ret[n] + reward;
-    const int new_len = s.run_len[n] + 1;
-    const float ep_ret = done ? new_ret : s.ep_ret[n];
-    const int ep_len = done ? new_len : s.ep_len[n];
-    s.run_ret[n] = done ? 0.f : new_ret;
-    s.run_len[n] = done ? 0 : new_len;
-    s.ep_ret[n] = ep_ret;
-    s.ep_len[n] = ep_len;
-    o.m_ep_ret[n] = ep_ret;
-    o.m_ep_len[n] = ep_len;
-    o.m_term[n] = done ? 1 : 0;
-  }
+  if (lane == 0) metrics_step(s.m, o, n, reward, done);   // the mean over agents of identical rewards == reward
 }
 
 }  // namespace magpo
@@ -172,8 +138,8 @@ extern "C" int magpo_coordsum_reset(int* step_count, int* target, int* record, u
                                     float* run_ret, int* run_len, float* ep_ret, int* ep_len, int N, int A, int K, int TLIM,
                                     int maxval, const uint32_t* env_keys, float* obs, int* obs_step, hipStream_t st) {
   if (int e = check_cfg(N, A, K, TLIM)) return e;
-  if (N == 0) return MAGPO_OK;
-  CoordSumState s{step_count, target, record, key, metrics_key, run_ret, run_len, ep_ret, ep_len};
+  if (int e = env_args(N); e != ENV_LAUNCH) return e;
+  CoordSumState s{step_count, target, record, key, {metrics_key, run_ret, run_len, ep_ret, ep_len}};
   CoordSumCfg c{N, A, K, TLIM, maxval};
   hipLaunchKernelGGL(k_coordsum_reset, dim3((N + 3) / 4), dim3(256), 0, st, s, c, env_keys, obs, obs_step);
   return check_launch("magpo_coordsum_reset");
@@ -185,10 +151,10 @@ extern "C" int magpo_coordsum_step(int* step_count, int* target, int* record, ui
                                    unsigned char* done, float* obs, int* obs_step, float* m_ep_ret, int* m_ep_len, unsigned char* m_term,
                                    int auto_reset, hipStream_t st) {
   if (int e = check_cfg(N, A, K, TLIM)) return e;
-  if (N == 0) return MAGPO_OK;
-  CoordSumState s{step_count, target, record, key, metrics_key, run_ret, run_len, ep_ret, ep_len};
+  if (int e = env_args(N); e != ENV_LAUNCH) return e;
+  CoordSumState s{step_count, target, record, key, {metrics_key, run_ret, run_len, ep_ret, ep_len}};
   CoordSumCfg c{N, A, K, TLIM, maxval};
-  StepOut o{reward, discount, done, obs, obs_step, m_ep_ret, m_ep_len, m_term};
+  StepOut o{reward, discount, done, obs, A + 1, obs_step, nullptr, m_ep_ret, m_ep_len, m_term};   // dense rows
   hipLaunchKernelGGL(k_coordsum_step, dim3((N + 3) / 4), dim3(256), 0, st, s, c, actions, act_stride, o, auto_reset);
   return check_launch("magpo_coordsum_step");
 }

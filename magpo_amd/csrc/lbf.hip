@@ -5,7 +5,7 @@
 // each other.  One thread per env: the state is a few dozen integers, so the kernel is a pure HBM stream
 // (state in, state + obs [A][3 (NF + A) + A] f32 + action mask [A][6] u8 out), coalesced across the envs of a wave by the
 // struct-of-arrays layout below.
-#include "common.hpp"
+#include "env_wrappers.hpp"
 
 namespace magpo {
 
@@ -21,8 +21,7 @@ struct LbfState {
   unsigned char* food_eaten;  // [N][NF]
   int* step_count;         // [N]
   uint32_t* key;           // [N][2]   LevelBasedForaging State.key
-  uint32_t* metrics_key;   // [N][2]   RecordEpisodeMetricsState.key (kept, never consumed)
-  float* run_ret; int* run_len; float* ep_ret; int* ep_len;  // [N]
+  EpisodeMetrics m;
 };
 struct LbfCfg { int N, A, NF, G, fov, max_level, force_coop, TLIM; };
 
@@ -36,8 +35,7 @@ __device__ __forceinline__ uint32_t rb32(uint32_t k0, uint32_t k1) { return rand
 __device__ __forceinline__ int lbf_randint(uint32_t k0, uint32_t k1, uint32_t i, int lo, int hi) {
   // jax.random.randint(key, (n,), lo, hi) element i (oracle/prng.py:randint)
   uint32_t a0, a1, b0, b1;
-  threefry2x32(k0, k1, 0u, 0u, a0, a1);
-  threefry2x32(k0, k1, 0u, 1u, b0, b1);
+  split_key(k0, k1, a0, a1, b0, b1);
   const uint32_t span = hi > lo ? (uint32_t)(hi - lo) : 1u;
   const uint32_t h = random_bits32(a0, a1, i), l = random_bits32(b0, b1, i);
   uint32_t mult = 65536u % span;
@@ -169,33 +167,24 @@ __device__ __forceinline__ void lbf_observe(const LbfCfg& c, const LbfEnv& e, fl
 
 __global__ __launch_bounds__(64) void k_lbf_reset(LbfState s, LbfCfg c, const uint32_t* __restrict__ env_keys, float* __restrict__ obs,
                                                   int* __restrict__ obs_step, unsigned char* __restrict__ mask) {
-  const long n = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= c.N) return;
-  const uint32_t e0 = env_keys[2 * n], e1 = env_keys[2 * n + 1];
-  uint32_t m0, m1, r0, r1, k0, k1;
-  threefry2x32(e0, e1, 0u, 0u, m0, m1);  // key, reset_key = split(key)   (episode_metrics.py:62)
-  threefry2x32(e0, e1, 0u, 1u, r0, r1);
+  long n;
+  if (!env_index(c.N, n)) return;
+  uint32_t r0, r1, k0, k1;
+  metrics_reset(s.m, n, env_keys[2 * n], env_keys[2 * n + 1], r0, r1);
   LbfEnv e;
   lbf_generate(c, r0, r1, e, k0, k1);
   lbf_store(s, c, n, e);
   s.step_count[n] = 0;
   s.key[2 * n] = k0; s.key[2 * n + 1] = k1;
-  s.metrics_key[2 * n] = m0; s.metrics_key[2 * n + 1] = m1;
-  s.run_ret[n] = 0.f; s.run_len[n] = 0; s.ep_ret[n] = 0.f; s.ep_len[n] = 0;
   const int F = c.A + 3 * (c.NF + c.A);
   lbf_observe(c, e, obs + n * (long)c.A * F, mask + n * (long)c.A * LBF_NACT);
   obs_step[n] = 0;
 }
 
-struct LbfOut {
-  float* reward; float* discount; unsigned char* done; float* obs; int* obs_step; unsigned char* mask;
-  float* m_ep_ret; int* m_ep_len; unsigned char* m_term;
-};
-
-__global__ __launch_bounds__(64) void k_lbf_step(LbfState s, LbfCfg c, const int* __restrict__ actions, int act_stride, LbfOut o,
+__global__ __launch_bounds__(64) void k_lbf_step(LbfState s, LbfCfg c, const int* __restrict__ actions, int act_stride, StepOut o,
                                                  int auto_reset) {
-  const long n = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= c.N) return;
+  long n;
+  if (!env_index(c.N, n)) return;
   const int A = c.A, NF = c.NF;
   LbfEnv e;
   lbf_load(s, c, n, e);
@@ -245,7 +234,7 @@ __global__ __launch_bounds__(64) void k_lbf_step(LbfState s, LbfCfg c, const int
   int obs_step = steps;
   if (done && auto_reset) {
     uint32_t k0 = s.key[2 * n], k1 = s.key[2 * n + 1], nk0, nk1, sk0, sk1;
-    threefry2x32(k0, k1, 0u, 0u, nk0, nk1);  // key, _ = split(state.key)   (auto_reset_wrapper.py:74)
+    split_key_first(k0, k1, nk0, nk1);
     lbf_generate(c, nk0, nk1, e, sk0, sk1);
     s.key[2 * n] = sk0; s.key[2 * n + 1] = sk1;
     obs_step = 0;
@@ -255,23 +244,8 @@ __global__ __launch_bounds__(64) void k_lbf_step(LbfState s, LbfCfg c, const int
   const int F = A + 3 * (NF + A);
   lbf_observe(c, e, o.obs + n * (long)A * F, o.mask + n * (long)A * LBF_NACT);
   o.obs_step[n] = obs_step;
-  for (int a = 0; a < A; ++a) o.reward[n * A + a] = team;
-  if (o.discount) for (int a = 0; a < A; ++a) o.discount[n * A + a] = all ? 0.f : 1.f;   // termination = all food eaten; the time limit truncates (discount 1)
-  o.done[n] = done ? 1 : 0;
-  // episode_metrics.py:79-112: mean over agents of the (identical) team rewards, as a sum / A in fp32
-  float msum = 0.f;
-  for (int a = 0; a < A; ++a) msum += team;
-  const float new_ret = s.run_ret[n] + __fdiv_rn(msum, (float)A);
-  const int new_len = s.run_len[n] + 1;
-  const float ep_ret = done ? new_ret : s.ep_ret[n];
-  const int ep_len = done ? new_len : s.ep_len[n];
-  s.run_ret[n] = done ? 0.f : new_ret;
-  s.run_len[n] = done ? 0 : new_len;
-  s.ep_ret[n] = ep_ret;
-  s.ep_len[n] = ep_len;
-  o.m_ep_ret[n] = ep_ret;
-  o.m_ep_len[n] = ep_len;
-  o.m_term[n] = done ? 1 : 0;
+  write_team_outputs(o, n, A, team, all, done);   // termination = all food eaten; the time limit truncates (discount 1)
+  metrics_step(s.m, o, n, team_mean(team, A), done);
 }
 
 }  // namespace magpo
@@ -295,11 +269,11 @@ extern "C" int magpo_lbf_reset(int* agent_pos, int* agent_level, int* food_pos, 
                                uint32_t* key, uint32_t* metrics_key, float* run_ret, int* run_len, float* ep_ret, int* ep_len, int N, int A,
                                int NF, int G, int fov, int max_level, int force_coop, int time_limit, const uint32_t* env_keys, float* obs,
                                int* obs_step, unsigned char* mask, hipStream_t st) {
-  LbfState s{agent_pos, agent_level, food_pos, food_level, food_eaten, step_count, key, metrics_key, run_ret, run_len, ep_ret, ep_len};
+  LbfState s{agent_pos, agent_level, food_pos, food_level, food_eaten, step_count, key, {metrics_key, run_ret, run_len, ep_ret, ep_len}};
   LbfCfg c{N, A, NF, G, fov, max_level, force_coop, time_limit};
   if (int e = lbf_check(c)) return e;
-  if (N <= 0) return MAGPO_OK;
-  hipLaunchKernelGGL(k_lbf_reset, dim3((N + 63) / 64), dim3(64), 0, st, s, c, env_keys, obs, obs_step, mask);
+  if (int e = env_args(N); e != ENV_LAUNCH) return e;
+  hipLaunchKernelGGL(k_lbf_reset, env_grid(N), dim3(ENV_BLOCK), 0, st, s, c, env_keys, obs, obs_step, mask);
   return check_launch("magpo_lbf_reset");
 }
 
@@ -308,11 +282,11 @@ extern "C" int magpo_lbf_step(int* agent_pos, int* agent_level, int* food_pos, i
                               int NF, int G, int fov, int max_level, int force_coop, int time_limit, const int* actions, int act_stride,
                               float* reward, float* discount, unsigned char* done, float* obs, int* obs_step, unsigned char* mask, float* m_ep_ret,
                               int* m_ep_len, unsigned char* m_term, int auto_reset, hipStream_t st) {
-  LbfState s{agent_pos, agent_level, food_pos, food_level, food_eaten, step_count, key, metrics_key, run_ret, run_len, ep_ret, ep_len};
+  LbfState s{agent_pos, agent_level, food_pos, food_level, food_eaten, step_count, key, {metrics_key, run_ret, run_len, ep_ret, ep_len}};
   LbfCfg c{N, A, NF, G, fov, max_level, force_coop, time_limit};
   if (int e = lbf_check(c)) return e;
-  if (N <= 0) return MAGPO_OK;
-  LbfOut o{reward, discount, done, obs, obs_step, mask, m_ep_ret, m_ep_len, m_term};
-  hipLaunchKernelGGL(k_lbf_step, dim3((N + 63) / 64), dim3(64), 0, st, s, c, actions, act_stride, o, auto_reset);
+  if (int e = env_args(N); e != ENV_LAUNCH) return e;
+  StepOut o{reward, discount, done, obs, A + 3 * (NF + A), obs_step, mask, m_ep_ret, m_ep_len, m_term};   // dense rows
+  hipLaunchKernelGGL(k_lbf_step, env_grid(N), dim3(ENV_BLOCK), 0, st, s, c, actions, act_stride, o, auto_reset);
   return check_launch("magpo_lbf_step");
 }

@@ -18,7 +18,7 @@
 // fp64 as max(x, 0) + log1p(exp(-|x|)) and rounded once to fp32 (JaxMARL's fp32 logaddexp may differ from it by less than an ulp).
 // One thread per env; its agents' positions, velocities and forces live in LDS ([6 A][64] floats per block, thread-minor so that a
 // wave's accesses hit 64 distinct banks), which keeps the runtime-indexed entity loops out of scratch.
-#include "common.hpp"
+#include "env_wrappers.hpp"
 
 #pragma clang fp contract(off)
 
@@ -32,8 +32,8 @@ struct MpState {
   float* vel;                             // [N][A][2]
   int* inner_step;                        // [N] SimpleMPE State.step
   int* step_count;                        // [N] JaxMarlState.step (the wrapper's counter)
-  uint32_t* key; uint32_t* metrics_key;   // [N][2]
-  float* run_ret; int* run_len; float* ep_ret; int* ep_len;
+  uint32_t* key;                          // [N][2]
+  EpisodeMetrics m;
 };
 struct MpCfg { int N, A, L, TLIM; float local_ratio; };
 
@@ -54,8 +54,7 @@ __device__ __forceinline__ float mp_uniform(uint32_t k0, uint32_t k1, uint32_t i
 __device__ void mp_inner_reset(const MpCfg& c, const MpState& s, long n, const MpLds& m, uint32_t k0, uint32_t k1) {
   const int A = c.A, L = c.L;
   uint32_t a0, a1, l0, l1;
-  threefry2x32(k0, k1, 0u, 0u, a0, a1);
-  threefry2x32(k0, k1, 0u, 1u, l0, l1);
+  split_key(k0, k1, a0, a1, l0, l1);
   float* pos = s.pos + n * (long)(A + L) * 2;
   float* vel = s.vel + n * (long)A * 2;
   for (int k = 0; k < 2 * A; ++k) {
@@ -70,8 +69,7 @@ __device__ void mp_inner_reset(const MpCfg& c, const MpState& s, long n, const M
 // the wrapper's reset (JaxMarlWrapper.reset): key, reset_key = split(key); the inner reset on reset_key; the counter starts at 0
 __device__ void mp_wrapper_reset(const MpCfg& c, const MpState& s, long n, const MpLds& m, uint32_t k0, uint32_t k1) {
   uint32_t nk0, nk1, r0, r1;
-  threefry2x32(k0, k1, 0u, 0u, nk0, nk1);
-  threefry2x32(k0, k1, 0u, 1u, r0, r1);
+  split_key(k0, k1, nk0, nk1, r0, r1);
   mp_inner_reset(c, s, n, m, r0, r1);
   s.key[2 * n] = nk0; s.key[2 * n + 1] = nk1;
   s.step_count[n] = 0;
@@ -129,29 +127,20 @@ __device__ void mp_observe(const MpCfg& c, const MpState& s, long n, const MpLds
 __global__ __launch_bounds__(MP_BLK) void k_mpe_reset(MpState s, MpCfg c, const uint32_t* __restrict__ env_keys, float* __restrict__ obs, long ldo,
                                                       int* __restrict__ obs_step) {
   extern __shared__ float mp_lds[];
-  const long n = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= c.N) return;
+  long n;
+  if (!env_index(c.N, n)) return;
   const MpLds m{mp_lds + threadIdx.x, c.A};
-  const uint32_t e0 = env_keys[2 * n], e1 = env_keys[2 * n + 1];
-  uint32_t m0, m1, r0, r1;
-  threefry2x32(e0, e1, 0u, 0u, m0, m1);  // key, reset_key = split(key)   (episode_metrics.py:62)
-  threefry2x32(e0, e1, 0u, 1u, r0, r1);
+  uint32_t r0, r1;
+  metrics_reset(s.m, n, env_keys[2 * n], env_keys[2 * n + 1], r0, r1);
   mp_wrapper_reset(c, s, n, m, r0, r1);
-  s.metrics_key[2 * n] = m0; s.metrics_key[2 * n + 1] = m1;
-  s.run_ret[n] = 0.f; s.run_len[n] = 0; s.ep_ret[n] = 0.f; s.ep_len[n] = 0;
   mp_observe(c, s, n, m, obs + n * (long)c.A * ldo, ldo);
   obs_step[n] = 0;
 }
 
-struct MpOut {
-  float* reward; float* discount; unsigned char* done; float* obs; long ldo; int* obs_step;
-  float* m_ep_ret; int* m_ep_len; unsigned char* m_term;
-};
-
-__global__ __launch_bounds__(MP_BLK) void k_mpe_step(MpState s, MpCfg c, const int* __restrict__ actions, int act_stride, MpOut o, int auto_reset) {
+__global__ __launch_bounds__(MP_BLK) void k_mpe_step(MpState s, MpCfg c, const int* __restrict__ actions, int act_stride, StepOut o, int auto_reset) {
   extern __shared__ float mp_lds[];
-  const long n = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= c.N) return;
+  long n;
+  if (!env_index(c.N, n)) return;
   const MpLds m{mp_lds + threadIdx.x, c.A};
   const int A = c.A, L = c.L;
   float* pos = s.pos + n * (long)(A + L) * 2;
@@ -160,8 +149,7 @@ __global__ __launch_bounds__(MP_BLK) void k_mpe_step(MpState s, MpCfg c, const i
   for (int k = 0; k < 2 * A; ++k) { m.p(k) = pos[k]; m.v(k) = vel[k]; }
   // JaxMarlWrapper.step: key, step_key = split(state.key)
   uint32_t k0, k1, sk0, sk1;
-  threefry2x32(s.key[2 * n], s.key[2 * n + 1], 0u, 0u, k0, k1);
-  threefry2x32(s.key[2 * n], s.key[2 * n + 1], 0u, 1u, sk0, sk1);
+  split_key(s.key[2 * n], s.key[2 * n + 1], k0, k1, sk0, sk1);
   s.key[2 * n] = k0; s.key[2 * n + 1] = k1;
   // world step on the pre-step positions
   const float dmin = MP_RAD + MP_RAD;
@@ -213,7 +201,7 @@ __global__ __launch_bounds__(MP_BLK) void k_mpe_step(MpState s, MpCfg c, const i
   if (done) {
     if (auto_reset) {
       uint32_t a0, a1;
-      threefry2x32(k0, k1, 0u, 0u, a0, a1);   // key, _ = split(state.key)   (auto_reset_wrapper.py:74)
+      split_key_first(k0, k1, a0, a1);
       mp_wrapper_reset(c, s, n, m, a0, a1);
       obs_step = 0;
     } else {
@@ -224,19 +212,8 @@ __global__ __launch_bounds__(MP_BLK) void k_mpe_step(MpState s, MpCfg c, const i
   }
   mp_observe(c, s, n, m, o.obs + n * (long)A * o.ldo, o.ldo);
   o.obs_step[n] = obs_step;
-  if (o.discount) for (int a = 0; a < A; ++a) o.discount[n * A + a] = done ? 0.f : 1.f;
-  o.done[n] = done ? 1 : 0;
-  const float new_ret = s.run_ret[n] + __fdiv_rn(msum, (float)A);
-  const int new_len = s.run_len[n] + 1;
-  const float ep_ret = done ? new_ret : s.ep_ret[n];
-  const int ep_len = done ? new_len : s.ep_len[n];
-  s.run_ret[n] = done ? 0.f : new_ret;
-  s.run_len[n] = done ? 0 : new_len;
-  s.ep_ret[n] = ep_ret;
-  s.ep_len[n] = ep_len;
-  o.m_ep_ret[n] = ep_ret;
-  o.m_ep_len[n] = ep_len;
-  o.m_term[n] = done ? 1 : 0;
+  write_discount_done(o, n, A, done, done);
+  metrics_step(s.m, o, n, __fdiv_rn(msum, (float)A), done);
 }
 
 }  // namespace magpo
@@ -260,9 +237,9 @@ extern "C" int magpo_mpe_reset(float* pos, float* vel, int* inner_step, int* ste
                                const uint32_t* env_keys, float* obs, long ldo, int* obs_step, hipStream_t st) {
   MpCfg c;
   if (int e = mp_cfg(c, N, A, L, time_limit, local_ratio, ldo)) return e;
-  if (N <= 0) return MAGPO_OK;
-  MpState s{pos, vel, inner_step, step_count, key, metrics_key, run_ret, run_len, ep_ret, ep_len};
-  hipLaunchKernelGGL(k_mpe_reset, dim3((N + MP_BLK - 1) / MP_BLK), dim3(MP_BLK), mp_lds_bytes(A), st, s, c, env_keys, obs, ldo, obs_step);
+  if (int e = env_args(N); e != ENV_LAUNCH) return e;
+  MpState s{pos, vel, inner_step, step_count, key, {metrics_key, run_ret, run_len, ep_ret, ep_len}};
+  hipLaunchKernelGGL(k_mpe_reset, env_grid(N, MP_BLK), dim3(MP_BLK), mp_lds_bytes(A), st, s, c, env_keys, obs, ldo, obs_step);
   return check_launch("magpo_mpe_reset");
 }
 
@@ -272,10 +249,9 @@ extern "C" int magpo_mpe_step(float* pos, float* vel, int* inner_step, int* step
                               float* m_ep_ret, int* m_ep_len, unsigned char* m_term, int auto_reset, hipStream_t st) {
   MpCfg c;
   if (int e = mp_cfg(c, N, A, L, time_limit, local_ratio, ldo)) return e;
-  if (N <= 0) return MAGPO_OK;
-  if (act_stride < A) { set_error("mpe: act_stride < num_agents"); return MAGPO_EINVAL; }
-  MpState s{pos, vel, inner_step, step_count, key, metrics_key, run_ret, run_len, ep_ret, ep_len};
-  MpOut o{reward, discount, done, obs, ldo, obs_step, m_ep_ret, m_ep_len, m_term};
-  hipLaunchKernelGGL(k_mpe_step, dim3((N + MP_BLK - 1) / MP_BLK), dim3(MP_BLK), mp_lds_bytes(A), st, s, c, actions, act_stride, o, auto_reset);
+  if (int e = env_args(N, A, act_stride, "mpe: act_stride < num_agents"); e != ENV_LAUNCH) return e;
+  MpState s{pos, vel, inner_step, step_count, key, {metrics_key, run_ret, run_len, ep_ret, ep_len}};
+  StepOut o{reward, discount, done, obs, ldo, obs_step, nullptr, m_ep_ret, m_ep_len, m_term};
+  hipLaunchKernelGGL(k_mpe_step, env_grid(N, MP_BLK), dim3(MP_BLK), mp_lds_bytes(A), st, s, c, actions, act_stride, o, auto_reset);
   return check_launch("magpo_mpe_step");
 }

@@ -5,7 +5,7 @@
 // bit-exact with each other.  One thread per env working in place on the env's grids in HBM (two H x W int layers):
 // a step touches a few dozen cells, the observation window and the outputs, so the kernel is a small latency-bound
 // stream next to the acting kernel.
-#include "common.hpp"
+#include "env_wrappers.hpp"
 
 namespace magpo {
 
@@ -19,8 +19,8 @@ struct RwState {
   int* queue;                        // [N][Q] requested shelf ids (1-based)
   int* step_count;                   // [N]
   unsigned char* amask;              // [N][A][5] action mask of the current state (sanitises the next actions)
-  uint32_t* key; uint32_t* metrics_key;   // [N][2]
-  float* run_ret; int* run_len; float* ep_ret; int* ep_len;
+  uint32_t* key;                     // [N][2]
+  EpisodeMetrics m;
 };
 struct RwCfg { int N, A, CH, SR, SC, R, Q, TLIM, H, W, NS; };
 
@@ -34,8 +34,7 @@ __device__ __forceinline__ void rw_ahead(const RwCfg& c, int r, int q, int d, in
 }
 __device__ __forceinline__ int rw_randint4(uint32_t k0, uint32_t k1, uint32_t i) {   // jax.random.randint(key, (n,), 0, 4) element i
   uint32_t a0, a1, b0, b1;
-  threefry2x32(k0, k1, 0u, 0u, a0, a1);
-  threefry2x32(k0, k1, 0u, 1u, b0, b1);
+  split_key(k0, k1, a0, a1, b0, b1);
   const uint32_t h = random_bits32(a0, a1, i), l = random_bits32(b0, b1, i);
   const uint32_t mult = ((65536u % 4u) * (65536u % 4u)) % 4u;
   return (int)(((h % 4u) * mult + (l % 4u)) % 4u);
@@ -145,27 +144,18 @@ __device__ __forceinline__ void rw_observe(const RwCfg& c, const RwState& s, lon
 
 __global__ __launch_bounds__(64) void k_rware_reset(RwState s, RwCfg c, const uint32_t* __restrict__ env_keys, float* __restrict__ obs, long ldo,
                                                     int* __restrict__ obs_step, unsigned char* __restrict__ mask) {
-  const long n = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= c.N) return;
-  const uint32_t e0 = env_keys[2 * n], e1 = env_keys[2 * n + 1];
-  uint32_t m0, m1, r0, r1;
-  threefry2x32(e0, e1, 0u, 0u, m0, m1);  // key, reset_key = split(key)   (episode_metrics.py:62)
-  threefry2x32(e0, e1, 0u, 1u, r0, r1);
+  long n;
+  if (!env_index(c.N, n)) return;
+  uint32_t r0, r1;
+  metrics_reset(s.m, n, env_keys[2 * n], env_keys[2 * n + 1], r0, r1);
   rw_generate(c, s, n, r0, r1);
-  s.metrics_key[2 * n] = m0; s.metrics_key[2 * n + 1] = m1;
-  s.run_ret[n] = 0.f; s.run_len[n] = 0; s.ep_ret[n] = 0.f; s.ep_len[n] = 0;
   rw_observe(c, s, n, obs + n * (long)c.A * ldo, ldo, mask + n * (long)c.A * RW_NACT);
   obs_step[n] = 0;
 }
 
-struct RwOut {
-  float* reward; float* discount; unsigned char* done; float* obs; long ldo; int* obs_step; unsigned char* mask;
-  float* m_ep_ret; int* m_ep_len; unsigned char* m_term;
-};
-
-__global__ __launch_bounds__(64) void k_rware_step(RwState s, RwCfg c, const int* __restrict__ actions, int act_stride, RwOut o, int auto_reset) {
-  const long n = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= c.N) return;
+__global__ __launch_bounds__(64) void k_rware_step(RwState s, RwCfg c, const int* __restrict__ actions, int act_stride, StepOut o, int auto_reset) {
+  long n;
+  if (!env_index(c.N, n)) return;
   const int A = c.A, HW = c.H * c.W;
   int* ga = s.grid_a + n * HW; int* gs = s.grid_s + n * HW;
   int act[RW_MAXA];
@@ -206,8 +196,7 @@ __global__ __launch_bounds__(64) void k_rware_step(RwState s, RwCfg c, const int
     if (sid > 0 && req[sid - 1]) {
       reward += 1.0f;
       uint32_t n0, n1, s0, s1;
-      threefry2x32(k0, k1, 0u, 0u, n0, n1);   // key, sub = split(key)
-      threefry2x32(k0, k1, 0u, 1u, s0, s1);
+      split_key(k0, k1, n0, n1, s0, s1);   // key, sub = split(key)
       k0 = n0; k1 = n1;
       // the replacement request: choice(sub, NS, (), replace=False, p=not requested) = Gumbel top-1 (oracle/prng.py:choice): the first
       // maximum of gumbel(sub, (NS,))[i] over the shelves that are not in the queue (the delivered one still counts as requested)
@@ -232,7 +221,7 @@ __global__ __launch_bounds__(64) void k_rware_step(RwState s, RwCfg c, const int
   int obs_step = steps;
   if (done && auto_reset) {
     uint32_t nk0, nk1;
-    threefry2x32(k0, k1, 0u, 0u, nk0, nk1);  // key, _ = split(state.key)   (auto_reset_wrapper.py:74)
+    split_key_first(k0, k1, nk0, nk1);
     rw_generate(c, s, n, nk0, nk1);
     obs_step = 0;
   } else {
@@ -241,22 +230,8 @@ __global__ __launch_bounds__(64) void k_rware_step(RwState s, RwCfg c, const int
   }
   rw_observe(c, s, n, o.obs + n * (long)A * o.ldo, o.ldo, o.mask + n * (long)A * RW_NACT);
   o.obs_step[n] = obs_step;
-  for (int a = 0; a < A; ++a) o.reward[n * A + a] = reward;
-  if (o.discount) for (int a = 0; a < A; ++a) o.discount[n * A + a] = done ? 0.f : 1.f;   // collision or horizon: termination
-  o.done[n] = done ? 1 : 0;
-  float msum = 0.f;   // episode_metrics.py:79-112: mean over agents of the repeated reward, as a sum / A in fp32
-  for (int a = 0; a < A; ++a) msum += reward;
-  const float new_ret = s.run_ret[n] + __fdiv_rn(msum, (float)A);
-  const int new_len = s.run_len[n] + 1;
-  const float ep_ret = done ? new_ret : s.ep_ret[n];
-  const int ep_len = done ? new_len : s.ep_len[n];
-  s.run_ret[n] = done ? 0.f : new_ret;
-  s.run_len[n] = done ? 0 : new_len;
-  s.ep_ret[n] = ep_ret;
-  s.ep_len[n] = ep_len;
-  o.m_ep_ret[n] = ep_ret;
-  o.m_ep_len[n] = ep_len;
-  o.m_term[n] = done ? 1 : 0;
+  write_team_outputs(o, n, A, reward, done, done);   // collision or horizon: termination
+  metrics_step(s.m, o, n, team_mean(reward, A), done);
 }
 
 }  // namespace magpo
@@ -293,9 +268,10 @@ extern "C" int magpo_rware_reset(int* grid_a, int* grid_s, int* agent_pos, int* 
                                  unsigned char* mask, hipStream_t st) {
   RwCfg c;
   if (int e = rw_cfg(c, N, A, column_height, shelf_rows, shelf_columns, sensor_range, queue_size, time_limit)) return e;
-  if (N <= 0) return MAGPO_OK;
-  RwState s{grid_a, grid_s, agent_pos, agent_dir, agent_carry, shelf_req, queue, step_count, amask, key, metrics_key, run_ret, run_len, ep_ret, ep_len};
-  hipLaunchKernelGGL(k_rware_reset, dim3((N + 63) / 64), dim3(64), 0, st, s, c, env_keys, obs, ldo, obs_step, mask);
+  if (int e = env_args(N); e != ENV_LAUNCH) return e;
+  RwState s{grid_a, grid_s, agent_pos, agent_dir, agent_carry, shelf_req, queue, step_count, amask, key,
+            {metrics_key, run_ret, run_len, ep_ret, ep_len}};
+  hipLaunchKernelGGL(k_rware_reset, env_grid(N), dim3(ENV_BLOCK), 0, st, s, c, env_keys, obs, ldo, obs_step, mask);
   return check_launch("magpo_rware_reset");
 }
 
@@ -307,9 +283,10 @@ extern "C" int magpo_rware_step(int* grid_a, int* grid_s, int* agent_pos, int* a
                                 unsigned char* m_term, int auto_reset, hipStream_t st) {
   RwCfg c;
   if (int e = rw_cfg(c, N, A, column_height, shelf_rows, shelf_columns, sensor_range, queue_size, time_limit)) return e;
-  if (N <= 0) return MAGPO_OK;
-  RwState s{grid_a, grid_s, agent_pos, agent_dir, agent_carry, shelf_req, queue, step_count, amask, key, metrics_key, run_ret, run_len, ep_ret, ep_len};
-  RwOut o{reward, discount, done, obs, ldo, obs_step, mask, m_ep_ret, m_ep_len, m_term};
-  hipLaunchKernelGGL(k_rware_step, dim3((N + 63) / 64), dim3(64), 0, st, s, c, actions, act_stride, o, auto_reset);
+  if (int e = env_args(N); e != ENV_LAUNCH) return e;
+  RwState s{grid_a, grid_s, agent_pos, agent_dir, agent_carry, shelf_req, queue, step_count, amask, key,
+            {metrics_key, run_ret, run_len, ep_ret, ep_len}};
+  StepOut o{reward, discount, done, obs, ldo, obs_step, mask, m_ep_ret, m_ep_len, m_term};
+  hipLaunchKernelGGL(k_rware_step, env_grid(N), dim3(ENV_BLOCK), 0, st, s, c, actions, act_stride, o, auto_reset);
   return check_launch("magpo_rware_step");
 }

@@ -23,6 +23,9 @@ import torch
 
 from ._lib import lib
 from .actor import GruActor
+# the environments live in envs.py; their names are re-exported here for the callers that import them from the learner
+from .envs import (ConnectorEnvBatch, CoordSumConfig, CoordSumEnvBatch, LbfConfig, LbfEnvBatch, MpeConfig, MpeEnvBatch, RwareConfig,  # noqa: F401
+                   RwareEnvBatch, VectorConnectorConfig, host_split, make_env_batch, net_obs, obs_row_stride, prng_key)
 from .sable import SableGuider
 
 
@@ -49,291 +52,6 @@ class SystemConfig:
     # ONE optimiser step (same gradient up to fp32 summation order; advantage statistics stay those of the whole minibatch).
     # Activations in HBM scale with the slab, so large teams run at the reference's num_minibatches within the memory of one GPU.
     micro_batches: int = 1
-
-
-@dataclass
-class CoordSumConfig:
-    num_agents: int
-    num_actions: int
-    time_limit: int = 100
-    maxval: Optional[int] = None
-    add_agent_id: bool = True  # system.add_agent_id (AgentIDWrapper, make_env.py:90-104): False = the networks read the rows behind the one-hot id
-    has_mask = False          # action_mask is all-True (matrax.py:117-134): never stored
-    class_tables = True       # observations take few distinct values: first-layer class tables apply (csrc/classtab.hip)
-
-    def __post_init__(self):
-        if not self.maxval:
-            self.maxval = self.num_actions  # coordsum/env.py:49-53
-
-    @property
-    def obs_dim(self) -> int:   # AgentIDWrapper (observation.py:42-54): [one-hot id | target]
-        return self.num_agents + 1
-
-
-@dataclass
-class LbfConfig:
-    """jumanji LevelBasedForaging-v0 + RandomGenerator(**task_config) (configs/env/scenario/*-coop.yaml) under LbfWrapper."""
-    grid_size: int = 8
-    fov: int = 8
-    num_agents: int = 2
-    num_food: int = 2
-    max_agent_level: int = 2
-    force_coop: bool = True
-    time_limit: int = 100
-    add_agent_id: bool = True
-    has_mask = True
-    class_tables = False
-    num_actions = 6
-
-    @property
-    def obs_dim(self) -> int:   # vector observation 3 (num_food + num_agents) + one-hot agent id
-        return 3 * (self.num_food + self.num_agents) + self.num_agents
-
-
-def net_obs(cfg) -> Tuple[int, int]:
-    """(features the networks read, column offset of the first one inside an observation row).  The env kernels always write
-    [one-hot agent id | features] rows (AgentIDWrapper, observation.py:42-54); with ``system.add_agent_id: False`` (make_env.py:90-104: the
-    wrapper is not applied) the networks are built for the features alone and every consumer gets the row pointer advanced by num_agents
-    floats with the row stride unchanged.  Narrow observations only (the 128-float padded rows of wide observations are read with
-    16-byte vector loads that a column offset would misalign)."""
-    if getattr(cfg, "add_agent_id", True):
-        return cfg.obs_dim, 0
-    if cfg.obs_dim > 32:
-        raise NotImplementedError("system.add_agent_id=False with wide observations (obs_dim > 32: Robot Warehouse)")
-    return cfg.obs_dim - cfg.num_agents, cfg.num_agents
-
-
-def host_split(key: np.ndarray, num: int = 2) -> np.ndarray:
-    """jax.random.split of one key on the host (exact; C ABI magpo_key_split_host)."""
-    key = np.ascontiguousarray(key, dtype=np.uint32)
-    out = np.empty((num, 2), np.uint32)
-    lib().raw("magpo_key_split_host")(key.ctypes.data, num, out.ctypes.data)
-    return out
-
-
-def prng_key(seed: int) -> np.ndarray:
-    return np.array([(int(seed) >> 32) & 0xFFFFFFFF, int(seed) & 0xFFFFFFFF], np.uint32)
-
-
-class CoordSumEnvBatch:
-    """Device-resident batch of wrapped CoordSum envs (state surface of coordsum/env.py:17-26 plus the
-    RecordEpisodeMetrics counters, episode_metrics.py:35-48)."""
-
-    def __init__(self, cfg: CoordSumConfig, N: int, device):
-        self.cfg, self.N, self.dev = cfg, N, device
-        A, K, TL = cfg.num_agents, cfg.num_actions, cfg.time_limit
-        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
-        self.step_count, self.target, self.record = i32(N), i32(N, TL + 1), i32(N, K, TL)
-        self.key, self.metrics_key = i32(N, 2), i32(N, 2)
-        self.run_ret, self.run_len = torch.zeros(N, device=device), i32(N)
-        self.ep_ret, self.ep_len = torch.zeros(N, device=device), i32(N)
-        self.L = lib()
-
-    def _state(self):
-        return (self.step_count, self.target, self.record, self.key, self.metrics_key, self.run_ret, self.run_len, self.ep_ret, self.ep_len)
-
-    def _cfg(self):
-        c = self.cfg
-        return (self.N, c.num_agents, c.num_actions, c.time_limit, c.maxval)
-
-    state_fields = ("step_count", "target", "record", "key", "metrics_key", "run_ret", "run_len", "ep_ret", "ep_len")
-
-    def reset(self, env_keys: torch.Tensor, obs, obs_step, mask=None):
-        self.L.call("magpo_coordsum_reset", *self._state(), *self._cfg(), env_keys, obs, obs_step, torch.cuda.current_stream().cuda_stream)
-
-    def step(self, actions, reward, done, obs, obs_step, m_ret, m_len, m_term, auto_reset=True, mask=None, discount=None):
-        self.L.call("magpo_coordsum_step", *self._state(), *self._cfg(), actions, self.cfg.num_agents, reward, discount, done, obs, obs_step,
-                    m_ret, m_len, m_term, 1 if auto_reset else 0, torch.cuda.current_stream().cuda_stream)
-
-
-class LbfEnvBatch:
-    """Device-resident batch of wrapped Level-Based Foraging envs (csrc/lbf.hip; UNPINNED dynamics, see oracle/lbf.py)."""
-    state_fields = ("agent_pos", "agent_level", "food_pos", "food_level", "food_eaten", "step_count", "key", "metrics_key",
-                    "run_ret", "run_len", "ep_ret", "ep_len")
-
-    def __init__(self, cfg: LbfConfig, N: int, device):
-        self.cfg, self.N, self.dev = cfg, N, device
-        A, NF = cfg.num_agents, cfg.num_food
-        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
-        self.agent_pos, self.agent_level, self.food_pos, self.food_level = i32(N, A, 2), i32(N, A), i32(N, NF, 2), i32(N, NF)
-        self.food_eaten = torch.zeros(N, NF, dtype=torch.uint8, device=device)
-        self.step_count, self.key, self.metrics_key = i32(N), i32(N, 2), i32(N, 2)
-        self.run_ret, self.run_len = torch.zeros(N, device=device), i32(N)
-        self.ep_ret, self.ep_len = torch.zeros(N, device=device), i32(N)
-        self.L = lib()
-
-    def _args(self):
-        c = self.cfg
-        return (self.agent_pos, self.agent_level, self.food_pos, self.food_level, self.food_eaten, self.step_count, self.key, self.metrics_key,
-                self.run_ret, self.run_len, self.ep_ret, self.ep_len, self.N, c.num_agents, c.num_food, c.grid_size, c.fov, c.max_agent_level,
-                1 if c.force_coop else 0, c.time_limit)
-
-    def reset(self, env_keys: torch.Tensor, obs, obs_step, mask=None):
-        self.L.call("magpo_lbf_reset", *self._args(), env_keys, obs, obs_step, mask, torch.cuda.current_stream().cuda_stream)
-
-    def step(self, actions, reward, done, obs, obs_step, m_ret, m_len, m_term, auto_reset=True, mask=None, discount=None):
-        self.L.call("magpo_lbf_step", *self._args(), actions, self.cfg.num_agents, reward, discount, done, obs, obs_step, mask, m_ret, m_len, m_term,
-                    1 if auto_reset else 0, torch.cuda.current_stream().cuda_stream)
-
-
-@dataclass
-class RwareConfig:
-    """jumanji RobotWarehouse-v0 + RandomGenerator(**task_config) (configs/env/scenario/tiny-4ag.yaml ...) under RwareWrapper."""
-    column_height: int = 8
-    shelf_rows: int = 1
-    shelf_columns: int = 3
-    num_agents: int = 4
-    sensor_range: int = 1
-    request_queue_size: int = 4
-    time_limit: int = 500
-    has_mask = True
-    class_tables = False
-    num_actions = 5
-
-    @property
-    def obs_dim(self) -> int:   # 8 + 7 (2 r + 1)^2 vector observation + one-hot agent id
-        return 8 + 7 * (2 * self.sensor_range + 1) ** 2 + self.num_agents
-
-
-class RwareEnvBatch:
-    """Device-resident batch of wrapped Robot Warehouse envs (csrc/rware.hip; UNPINNED dynamics, see oracle/rware.py)."""
-    state_fields = ("grid_a", "grid_s", "agent_pos", "agent_dir", "agent_carry", "shelf_req", "queue", "step_count", "amask", "key",
-                    "metrics_key", "run_ret", "run_len", "ep_ret", "ep_len")
-
-    def __init__(self, cfg: RwareConfig, N: int, device):
-        self.cfg, self.N, self.dev = cfg, N, device
-        self.L = lib()
-        lay = np.zeros(3, np.int32)
-        self.L.call("magpo_rware_layout", cfg.column_height, cfg.shelf_rows, cfg.shelf_columns, lay.ctypes.data)
-        self.H, self.W, self.NS = int(lay[0]), int(lay[1]), int(lay[2])
-        A = cfg.num_agents
-        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
-        u8 = lambda *s: torch.zeros(*s, dtype=torch.uint8, device=device)
-        self.grid_a, self.grid_s = i32(N, self.H, self.W), i32(N, self.H, self.W)
-        self.agent_pos, self.agent_dir, self.agent_carry = i32(N, A, 2), i32(N, A), u8(N, A)
-        self.shelf_req, self.queue = u8(N, self.NS), i32(N, cfg.request_queue_size)
-        self.step_count, self.amask, self.key, self.metrics_key = i32(N), u8(N, A, 5), i32(N, 2), i32(N, 2)
-        self.run_ret, self.run_len = torch.zeros(N, device=device), i32(N)
-        self.ep_ret, self.ep_len = torch.zeros(N, device=device), i32(N)
-        self.ldo = obs_row_stride(cfg.obs_dim)
-
-    def _args(self):
-        c = self.cfg
-        return (self.grid_a, self.grid_s, self.agent_pos, self.agent_dir, self.agent_carry, self.shelf_req, self.queue, self.step_count, self.amask,
-                self.key, self.metrics_key, self.run_ret, self.run_len, self.ep_ret, self.ep_len, self.N, c.num_agents, c.column_height,
-                c.shelf_rows, c.shelf_columns, c.sensor_range, c.request_queue_size, c.time_limit)
-
-    def reset(self, env_keys: torch.Tensor, obs, obs_step, mask=None):
-        self.L.call("magpo_rware_reset", *self._args(), env_keys, obs, self.ldo, obs_step, mask, torch.cuda.current_stream().cuda_stream)
-
-    def step(self, actions, reward, done, obs, obs_step, m_ret, m_len, m_term, auto_reset=True, mask=None, discount=None):
-        self.L.call("magpo_rware_step", *self._args(), actions, self.cfg.num_agents, reward, discount, done, obs, self.ldo, obs_step, mask, m_ret, m_len,
-                    m_term, 1 if auto_reset else 0, torch.cuda.current_stream().cuda_stream)
-
-
-@dataclass
-class VectorConnectorConfig:
-    """jumanji Connector-v2 + RandomWalkGenerator(**task_config) (configs/env/scenario/con-*.yaml) under VectorConnectorWrapper."""
-    grid_size: int = 10
-    num_agents: int = 10
-    time_limit: int = 100
-    has_mask = True
-    class_tables = False
-    num_actions = 5
-
-    @property
-    def obs_dim(self) -> int:   # 4 coordinates + two 5 x 5 windows + one-hot agent id
-        return 54 + self.num_agents
-
-
-class ConnectorEnvBatch:
-    """Device-resident batch of wrapped VectorConnector envs (csrc/connector.hip; UNPINNED dynamics, see its header comment)."""
-    state_fields = ("grid", "agent_start", "agent_target", "agent_pos", "step_count", "key", "metrics_key", "run_ret", "run_len", "ep_ret",
-                    "ep_len")
-
-    def __init__(self, cfg: VectorConnectorConfig, N: int, device):
-        self.cfg, self.N, self.dev = cfg, N, device
-        self.L = lib()
-        A, G = cfg.num_agents, cfg.grid_size
-        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
-        self.grid = i32(N, G, G)
-        self.agent_start, self.agent_target, self.agent_pos = i32(N, A, 2), i32(N, A, 2), i32(N, A, 2)
-        self.step_count, self.key, self.metrics_key = i32(N), i32(N, 2), i32(N, 2)
-        self.run_ret, self.run_len = torch.zeros(N, device=device), i32(N)
-        self.ep_ret, self.ep_len = torch.zeros(N, device=device), i32(N)
-        self.ldo = obs_row_stride(cfg.obs_dim)
-
-    def _args(self):
-        c = self.cfg
-        return (self.grid, self.agent_start, self.agent_target, self.agent_pos, self.step_count, self.key, self.metrics_key, self.run_ret,
-                self.run_len, self.ep_ret, self.ep_len, self.N, c.num_agents, c.grid_size, c.time_limit)
-
-    def reset(self, env_keys: torch.Tensor, obs, obs_step, mask=None):
-        self.L.call("magpo_connector_reset", *self._args(), env_keys, obs, self.ldo, obs_step, mask, torch.cuda.current_stream().cuda_stream)
-
-    def step(self, actions, reward, done, obs, obs_step, m_ret, m_len, m_term, auto_reset=True, mask=None, discount=None):
-        self.L.call("magpo_connector_step", *self._args(), actions, self.cfg.num_agents, reward, discount, done, obs, self.ldo, obs_step, mask,
-                    m_ret, m_len, m_term, 1 if auto_reset else 0, torch.cuda.current_stream().cuda_stream)
-
-
-@dataclass
-class MpeConfig:
-    """JaxMARL MPE_simple_spread_v3(**task_config) (configs/env/scenario/simple_spread_*.yaml), discrete actions, under MPEWrapper."""
-    num_agents: int = 3
-    num_landmarks: int = 3
-    local_ratio: float = 0.5
-    time_limit: int = 25        # SimpleMPE max_steps; an episode lasts time_limit + 1 steps (csrc/mpe.hip)
-    add_agent_id: bool = True   # system.add_agent_id: False = the networks read the rows behind the one-hot id (narrow rows only, net_obs)
-    has_mask = False            # every action is legal (MPEWrapper.action_mask): never stored
-    class_tables = False
-    num_actions = 5
-
-    @property
-    def obs_dim(self) -> int:   # vel, pos, landmarks, other agents' positions and (silent) comm + one-hot agent id
-        return 4 + 2 * self.num_landmarks + 4 * (self.num_agents - 1) + self.num_agents
-
-
-class MpeEnvBatch:
-    """Device-resident batch of wrapped MPE simple_spread envs (csrc/mpe.hip; UNPINNED dynamics, see tests/mpe_ref.py)."""
-    state_fields = ("pos", "vel", "inner_step", "step_count", "key", "metrics_key", "run_ret", "run_len", "ep_ret", "ep_len")
-
-    def __init__(self, cfg: MpeConfig, N: int, device):
-        self.cfg, self.N, self.dev = cfg, N, device
-        self.L = lib()
-        A, L = cfg.num_agents, cfg.num_landmarks
-        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
-        self.pos, self.vel = torch.zeros(N, A + L, 2, device=device), torch.zeros(N, A, 2, device=device)
-        self.inner_step, self.step_count, self.key, self.metrics_key = i32(N), i32(N), i32(N, 2), i32(N, 2)
-        self.run_ret, self.run_len = torch.zeros(N, device=device), i32(N)
-        self.ep_ret, self.ep_len = torch.zeros(N, device=device), i32(N)
-        self.ldo = obs_row_stride(cfg.obs_dim)
-
-    def _args(self):
-        c = self.cfg
-        return (self.pos, self.vel, self.inner_step, self.step_count, self.key, self.metrics_key, self.run_ret, self.run_len, self.ep_ret,
-                self.ep_len, self.N, c.num_agents, c.num_landmarks, c.time_limit, float(c.local_ratio))
-
-    def reset(self, env_keys: torch.Tensor, obs, obs_step, mask=None):
-        self.L.call("magpo_mpe_reset", *self._args(), env_keys, obs, self.ldo, obs_step, torch.cuda.current_stream().cuda_stream)
-
-    def step(self, actions, reward, done, obs, obs_step, m_ret, m_len, m_term, auto_reset=True, mask=None, discount=None):
-        self.L.call("magpo_mpe_step", *self._args(), actions, self.cfg.num_agents, reward, discount, done, obs, self.ldo, obs_step, m_ret, m_len,
-                    m_term, 1 if auto_reset else 0, torch.cuda.current_stream().cuda_stream)
-
-
-def obs_row_stride(obs_dim: int) -> int:
-    """Floats between observation rows: obs_dim for small observations, 128 (zero-padded) for wide ones (csrc/wideobs.hip)."""
-    return obs_dim if obs_dim <= 32 else 128
-
-
-def make_env_batch(cfg, N: int, device):
-    if isinstance(cfg, RwareConfig):
-        return RwareEnvBatch(cfg, N, device)
-    if isinstance(cfg, VectorConnectorConfig):
-        return ConnectorEnvBatch(cfg, N, device)
-    if isinstance(cfg, MpeConfig):
-        return MpeEnvBatch(cfg, N, device)
-    return LbfEnvBatch(cfg, N, device) if isinstance(cfg, LbfConfig) else CoordSumEnvBatch(cfg, N, device)
 
 
 class EnvGroup:

@@ -75,7 +75,7 @@ class SableGuider:
         # Robot Warehouse: the observation-side first layer then runs on the MFMA dense kernels, csrc/wideobs.hip)
         self.wide = obs_dim > 32
         self.Fld = 128 if self.wide else obs_dim      # floats between observation rows
-        if obs_ld is not None and int(obs_ld) != self.Fld:   # rows wider than the features read (system.add_agent_id: False, learner.net_obs)
+        if obs_ld is not None and int(obs_ld) != self.Fld:   # rows wider than the features read (system.add_agent_id: False, envs.net_obs)
             if self.wide or int(obs_ld) < obs_dim:
                 raise ValueError(f"obs_ld={obs_ld} with obs_dim={obs_dim}: a separate row stride is supported for narrow observations only")
             self.Fld = int(obs_ld)

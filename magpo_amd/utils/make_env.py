@@ -4,7 +4,8 @@ CoordSum (csrc/coordsum.hip), Level-Based Foraging (csrc/lbf.hip), Robot Warehou
 (csrc/connector.hip) and MPE simple_spread with discrete actions (csrc/mpe.hip) are implemented.  LBF / RWARE / Connector dynamics live in
 third-party Jumanji and MPE's in JaxMARL, both absent from the reference tree and from this image: all four are restated from the published
 algorithms with UNPINNED dynamics (oracle/lbf.py, oracle/rware.py, tests/connector_ref.py and tests/mpe_ref.py list every rule).  The
-grid-observation ``Connector`` (ConnectorWrapper) and MPE's continuous actions are not supported.
+grid-observation ``Connector`` (ConnectorWrapper) and MPE's continuous actions are not supported.  The wrapper stack the five kernels share
+is csrc/env_wrappers.hpp; the configs and the device-resident batches are magpo_amd/envs.py.
 """
 from __future__ import annotations
 
@@ -15,7 +16,7 @@ import numpy as np
 import torch
 
 from .. import specs
-from ..learner import CoordSumConfig, LbfConfig, MpeConfig, RwareConfig, VectorConnectorConfig, make_env_batch, net_obs, obs_row_stride
+from ..envs import CoordSumConfig, LbfConfig, MpeConfig, RwareConfig, VectorConnectorConfig, make_env_batch, net_obs, obs_row_stride
 from ..types import Observation, TimeStep
 
 COORDSUM_REGISTRY = {  # mava/coordsum/__init__.py:6-45
@@ -50,7 +51,7 @@ class MarlEnv:
     """The env API the system file, the learner set-up and the evaluator use (mava/types.py:45-123 ``MarlEnv``): ``num_agents`` /
     ``time_limit`` / ``action_dim``, ``reset(key) -> (state, timestep)``, ``step(state, action) -> (state, timestep)``,
     ``observation_spec`` / ``action_spec`` / ``reward_spec`` / ``discount_spec`` and ``unwrapped`` -- driving the HIP env kernels
-    (csrc/coordsum.hip, lbf.hip, rware.hip, connector.hip), which implement the whole wrapper stack of mava/utils/make_env.py:90-104
+    (csrc/coordsum.hip, lbf.hip, rware.hip, connector.hip, mpe.hip), which implement the whole wrapper stack of mava/utils/make_env.py:90-104
     (env wrapper -> AgentIDWrapper -> AutoResetWrapper [train env] -> RecordEpisodeMetrics).
 
     The batch axis is explicit: the reference calls ``jax.vmap(env.reset)(keys)`` / ``jax.vmap(env.step)(state, action)``; here
@@ -77,7 +78,6 @@ class MarlEnv:
     @property
     def obs_dim(self) -> int:
         """Width of ``agents_view`` as the networks see it: with the AgentIDWrapper's one-hot id, or (system.add_agent_id: False) without."""
-        from ..learner import net_obs
         return net_obs(self.cfg)[0]
 
     @property
@@ -115,7 +115,6 @@ class MarlEnv:
             if getattr(st, "_ones", None) is None or st._ones.shape[0] != N:
                 st._ones = torch.ones(N, A, K, dtype=torch.uint8, device=obs.device)
             mask = st._ones
-        from ..learner import net_obs
         off = net_obs(self.cfg)[1]     # the env kernels always write [one-hot id | features]: without the id the view starts behind it
         observation = Observation(obs[..., off:off + F], mask, obs_step.view(N, 1).expand(N, A))
         extras = {"episode_metrics": {"episode_return": m_ret, "episode_length": m_len, "is_terminal_step": m_term.bool()}, "env_metrics": {}}
@@ -160,19 +159,39 @@ class MarlEnv:
         return state, self._timestep(state, step_type, reward, discount, obs, obs_step, mask, m_ret, m_len, m_term)
 
 
-MarlEnvSpec = MarlEnv   # earlier name of this class
+def _kwargs_and_agent_id(config, *sources, name=None, allowed=(), note=""):
+    """The preamble of every factory: the env kwargs, later ``sources`` overriding earlier ones (make_env.py:107-135,211-213), refused unless
+    ``allowed`` holds them all (``name`` None: passed on unchecked); and system.add_agent_id as add_extra_wrappers resolves it
+    (make_env.py:90-104), written back to the config, where the network set-up reads it."""
+    kw = {}
+    for src in sources:
+        kw.update(src if isinstance(src, dict) else src.to_container())
+    unknown = set(kw) - set(allowed)
+    if name is not None and unknown:
+        raise NotImplementedError(f"{name} kwargs {sorted(unknown)} are not supported{note}")
+    add_id = bool(config.system.add_agent_id) and not bool(config.env.implicit_agent_id)
+    config.system.add_agent_id = add_id
+    return kw, add_id
+
+
+def _wide_rows_need_agent_id(add_id: bool, name: str):
+    if not add_id:
+        raise NotImplementedError(f"system.add_agent_id=False with {name}: its 128-float padded observation rows are read with 16-byte "
+                                  "vector loads that the column offset behind the one-hot id would misalign (CoordSum and LBF support it)")
+
+
+def _envs(cfg, add_id: bool):
+    """(train_env, eval_env): the eval env has no AutoResetWrapper (make_env.py:90-104)."""
+    return MarlEnv(cfg, auto_reset=True, add_agent_id=add_id), MarlEnv(cfg, auto_reset=False, add_agent_id=add_id)
 
 
 def make_coordsum_env(config):
     task = config.env.scenario.task_name
     if task not in COORDSUM_REGISTRY:
         raise ValueError(f"{task} is not a registered CoordSum scenario")
-    kw = dict(COORDSUM_REGISTRY[task])
-    kw.update(config.env.kwargs.to_container())  # **config.env.kwargs override the registered kwargs (make_env.py:211-213)
-    add_id = bool(config.system.add_agent_id) and not bool(config.env.implicit_agent_id)
-    config.system.add_agent_id = add_id
-    cfg = CoordSumConfig(**kw, add_agent_id=add_id)   # False: the networks read the rows behind the one-hot id (learner.net_obs)
-    return MarlEnvSpec(cfg, auto_reset=True, add_agent_id=add_id), MarlEnvSpec(cfg, auto_reset=False, add_agent_id=add_id)
+    # **config.env.kwargs override the registered kwargs (make_env.py:211-213)
+    kw, add_id = _kwargs_and_agent_id(config, COORDSUM_REGISTRY[task], config.env.kwargs)
+    return _envs(CoordSumConfig(**kw, add_agent_id=add_id), add_id)   # False: the networks read the rows behind the one-hot id (envs.net_obs)
 
 
 def make_lbf_env(config):
@@ -180,12 +199,8 @@ def make_lbf_env(config):
     kwargs = {**env.kwargs, **scenario.env_kwargs}; LbfWrapper's aggregate_rewards keeps its default True whatever
     env.aggregate_rewards says (the factory never passes it)."""
     tc = config.env.scenario.task_config.to_container()
-    kw = {**config.env.kwargs.to_container(), **config.env.scenario.env_kwargs.to_container()}
-    unknown = set(kw) - {"time_limit"}
-    if unknown:
-        raise NotImplementedError(f"LevelBasedForaging kwargs {sorted(unknown)} are not supported (grid observations, penalties, unnormalised rewards)")
-    add_id = bool(config.system.add_agent_id) and not bool(config.env.implicit_agent_id)
-    config.system.add_agent_id = add_id
+    kw, add_id = _kwargs_and_agent_id(config, config.env.kwargs, config.env.scenario.env_kwargs, name="LevelBasedForaging", allowed={"time_limit"},
+                                      note=" (grid observations, penalties, unnormalised rewards)")
     cfg = LbfConfig(grid_size=int(tc["grid_size"]), fov=int(tc["fov"]), num_agents=int(tc["num_agents"]), num_food=int(tc["num_food"]),
                     max_agent_level=int(tc.get("max_agent_level", 2)), force_coop=bool(tc.get("force_coop", False)),
                     time_limit=int(kw.get("time_limit", 100)), add_agent_id=add_id)
@@ -195,28 +210,21 @@ def make_lbf_env(config):
     if (G - 2) ** 2 < 5 * (cfg.num_food - 1) + 1 or G * G - cfg.num_food < cfg.num_agents:
         # a food blocks up to 5 interior cells for the later ones; jax.random.choice on an all-zero mask would silently return cell 0
         raise ValueError(f"LevelBasedForaging: a {G}x{G} grid cannot be guaranteed to hold {cfg.num_food} food items and {cfg.num_agents} agents")
-    return MarlEnvSpec(cfg, auto_reset=True), MarlEnvSpec(cfg, auto_reset=False)
+    return _envs(cfg, add_id)
 
 
 def make_rware_env(config):
     """make_jumanji_env (make_env.py:107-135) for RobotWarehouse: generator = RandomGenerator(**scenario.task_config), env kwargs =
     {**env.kwargs (time_limit: 500), **scenario.env_kwargs}, wrapped by RwareWrapper."""
     tc = config.env.scenario.task_config.to_container()
-    kw = {**config.env.kwargs.to_container(), **config.env.scenario.env_kwargs.to_container()}
-    unknown = set(kw) - {"time_limit"}
-    if unknown:
-        raise NotImplementedError(f"RobotWarehouse kwargs {sorted(unknown)} are not supported")
-    add_id = bool(config.system.add_agent_id) and not bool(config.env.implicit_agent_id)
-    config.system.add_agent_id = add_id
-    if not add_id:
-        raise NotImplementedError("system.add_agent_id=False with Robot Warehouse: its 128-float padded observation rows are read with 16-byte "
-                                  "vector loads that the column offset behind the one-hot id would misalign (CoordSum and LBF support it)")
+    kw, add_id = _kwargs_and_agent_id(config, config.env.kwargs, config.env.scenario.env_kwargs, name="RobotWarehouse", allowed={"time_limit"})
+    _wide_rows_need_agent_id(add_id, "Robot Warehouse")
     cfg = RwareConfig(column_height=int(tc["column_height"]), shelf_rows=int(tc["shelf_rows"]), shelf_columns=int(tc["shelf_columns"]),
                       num_agents=int(tc["num_agents"]), sensor_range=int(tc["sensor_range"]), request_queue_size=int(tc["request_queue_size"]),
                       time_limit=int(kw.get("time_limit", 500)))
     if cfg.sensor_range != 1:
         raise NotImplementedError("RobotWarehouse: sensor_range 1 only (observation rows are padded to 128 floats)")
-    return MarlEnvSpec(cfg, auto_reset=True), MarlEnvSpec(cfg, auto_reset=False)
+    return _envs(cfg, add_id)
 
 
 def make_vector_connector_env(config):
@@ -224,36 +232,25 @@ def make_vector_connector_env(config):
     RandomWalkGenerator(**scenario.task_config), env kwargs = {**env.kwargs, **scenario.env_kwargs} (time_limit only), wrapped by
     VectorConnectorWrapper with its default aggregate_rewards (the factory never passes env.aggregate_rewards, as for LBF)."""
     tc = config.env.scenario.task_config.to_container()
-    kw = {**config.env.kwargs.to_container(), **config.env.scenario.env_kwargs.to_container()}
-    unknown = set(kw) - {"time_limit"}
-    if unknown:
-        raise NotImplementedError(f"VectorConnector kwargs {sorted(unknown)} are not supported")
-    add_id = bool(config.system.add_agent_id) and not bool(config.env.implicit_agent_id)
-    config.system.add_agent_id = add_id
-    if not add_id:
-        raise NotImplementedError("system.add_agent_id=False with VectorConnector: its 128-float padded observation rows are read with 16-byte "
-                                  "vector loads that the column offset behind the one-hot id would misalign (CoordSum and LBF support it)")
+    kw, add_id = _kwargs_and_agent_id(config, config.env.kwargs, config.env.scenario.env_kwargs, name="VectorConnector", allowed={"time_limit"})
+    _wide_rows_need_agent_id(add_id, "VectorConnector")
     cfg = VectorConnectorConfig(grid_size=int(tc["grid_size"]), num_agents=int(tc["num_agents"]), time_limit=int(kw.get("time_limit", 100)))
     G, A = cfg.grid_size, cfg.num_agents
     if not (2 <= G <= 16 and 1 <= A <= 32 and A <= G * G):
         raise NotImplementedError("VectorConnector: 2 <= grid_size <= 16 and 1 <= num_agents <= min(32, grid_size^2) (csrc/connector.hip)")
-    return MarlEnvSpec(cfg, auto_reset=True), MarlEnvSpec(cfg, auto_reset=False)
+    return _envs(cfg, add_id)
 
 
 def make_mpe_env(config):
     """make_jaxmarl_env (make_env.py:138-170) for MPE: kwargs = {**env.kwargs, **scenario.task_config} for
     jaxmarl.make(scenario.name, **kwargs), wrapped by MPEWrapper (time_limit = the env's max_steps).  Discrete actions only."""
-    kw = {**config.env.kwargs.to_container(), **config.env.scenario.task_config.to_container()}
-    unknown = set(kw) - {"action_type", "num_agents", "num_landmarks", "local_ratio", "max_steps"}
-    if unknown:
-        raise NotImplementedError(f"MPE kwargs {sorted(unknown)} are not supported")
+    kw, add_id = _kwargs_and_agent_id(config, config.env.kwargs, config.env.scenario.task_config, name="MPE",
+                                      allowed={"action_type", "num_agents", "num_landmarks", "local_ratio", "max_steps"})
     action_type = kw.get("action_type", "Discrete")
     if action_type == "Continuous":
         raise NotImplementedError("MPE with continuous actions (tanh-Gaussian heads) is not supported: override env.kwargs.action_type=Discrete")
     if action_type != "Discrete":
         raise ValueError(f"MPE action_type {action_type!r}: 'Discrete' or 'Continuous'")
-    add_id = bool(config.system.add_agent_id) and not bool(config.env.implicit_agent_id)
-    config.system.add_agent_id = add_id
     cfg = MpeConfig(num_agents=int(kw.get("num_agents", 3)), num_landmarks=int(kw.get("num_landmarks", 3)),
                     local_ratio=float(kw.get("local_ratio", 0.5)), time_limit=int(kw.get("max_steps", 25)), add_agent_id=add_id)
     A, L = cfg.num_agents, cfg.num_landmarks
@@ -262,19 +259,15 @@ def make_mpe_env(config):
     if cfg.obs_dim > 128:
         raise NotImplementedError(f"MPE: observations of {cfg.obs_dim} floats (5 num_agents + 2 num_landmarks <= 128 required)")
     net_obs(cfg)   # system.add_agent_id=False needs narrow rows (3 agents: 18 features)
-    return MarlEnvSpec(cfg, auto_reset=True, add_agent_id=add_id), MarlEnvSpec(cfg, auto_reset=False, add_agent_id=add_id)
+    return _envs(cfg, add_id)
+
+
+FACTORIES = {"CoordSum": make_coordsum_env, "LevelBasedForaging": make_lbf_env, "RobotWarehouse": make_rware_env,
+             "VectorConnector": make_vector_connector_env, "MPE": make_mpe_env}
 
 
 def make(config):
     env_name = config.env.env_name
-    if env_name == "CoordSum":
-        return make_coordsum_env(config)
-    if env_name == "LevelBasedForaging":
-        return make_lbf_env(config)
-    if env_name == "RobotWarehouse":
-        return make_rware_env(config)
-    if env_name == "VectorConnector":
-        return make_vector_connector_env(config)
-    if env_name == "MPE":
-        return make_mpe_env(config)
-    raise ValueError(f"{env_name} is not a supported environment.")
+    if env_name not in FACTORIES:
+        raise ValueError(f"{env_name} is not a supported environment.")
+    return FACTORIES[env_name](config)
