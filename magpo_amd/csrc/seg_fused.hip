@@ -19,7 +19,7 @@ struct SegArgs {
   const float* r; const float* gp; long ldg; const float* gamma; const float* beta;
   const float* wo_t; const float* res; const float* s1; const float* s2;
   const float* pe; const int* pos; int npos;
-  float* u; float* y; float* o; float* ope;            // o / ope nullable
+  float* u; float* y; float* o; float* ope;            // all four nullable
   // tails
   const float* w0_t; const float* b0; float* out0; long ld0;          // ENC: vh0 -> hv ; DEC1: kvg2 (192) ; DEC2: h0 -> hp
   const float* hs; const float* hw; const float* hb1; float* value;   // ENC: head norm scale, value weights / bias
@@ -58,16 +58,16 @@ __device__ __forceinline__ Row dense64_reg(const Row& x, const float4 (&w)[4][4]
   }
   return y;
 }
-// same layer with the weight fragments read from an LDS copy of W^T ([64][WSP] floats: same products in the same order as dense64_reg)
-constexpr int WSP = 68;
-__device__ __forceinline__ Row dense64_lds(const Row& x, const float* __restrict__ ws, int m, int kq) {
+// same layer with the weight fragments read from a FRAGMENT-MAJOR LDS copy of W^T (same products in the same order as dense64_reg; wf[g][gk][lane][4] = W^T[16 g + m][16 gk + 4 kq ..]: one
+// ds_read_b128 reads 1 KB contiguous, no padding -- 16 KB per matrix); off = 4 * lane, passed in so that the caller can make it opaque
+__device__ __forceinline__ Row dense64_flds(const Row& x, const float* __restrict__ wf, int off) {
   Row y;
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int gk = 0; gk < 4; ++gk) {
-      const float4 w = *reinterpret_cast<const float4*>(ws + (16 * g + m) * WSP + 16 * gk + 4 * kq);
+      const float4 w = *reinterpret_cast<const float4*>(wf + (4 * g + gk) * 256 + off);
       acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, x.v[4 * gk], acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, x.v[4 * gk + 1], acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, x.v[4 * gk + 2], acc, 0, 0, 0);
@@ -76,6 +76,12 @@ __device__ __forceinline__ Row dense64_lds(const Row& x, const float* __restrict
     y.v[4 * g] = acc[0]; y.v[4 * g + 1] = acc[1]; y.v[4 * g + 2] = acc[2]; y.v[4 * g + 3] = acc[3];
   }
   return y;
+}
+__device__ __forceinline__ void fill_flds(float* __restrict__ wf, const float* __restrict__ Wt, int lane) {
+  const int m = lane & 15, kq = lane >> 4;
+#pragma unroll
+  for (int f = 0; f < 16; ++f)
+    *reinterpret_cast<float4*>(wf + f * 256 + 4 * lane) = ld4g(Wt + (long)(16 * (f >> 2) + m) * AE + 16 * (f & 3) + 4 * kq);
 }
 __device__ __forceinline__ void load_w64(float4 (&w)[4][4], const float* __restrict__ Wt, int m, int kq) {
 #pragma unroll
@@ -152,7 +158,7 @@ __global__ __launch_bounds__(64, 1) void k_seg_post(SegArgs a) {
     Row u;
 #pragma unroll
     for (int j = 0; j < 16; ++j) u.v[j] = fswish(g.v[j]) * ((r.v[j] - mu) * rstd * gam.v[j] + bet.v[j]);
-    row_store(a.u + rw * AE, kq, u);
+    if (a.u) row_store(a.u + rw * AE, kq, u);   // (only the unfused backward reads it: k_seg_bwd forms dW_o from its recomputed u)
     const Row y = dense64_reg(u, wo, nullptr, kq);
     if (a.y) row_store(a.y + rw * AE, kq, y);   // (not kept for the fused backward, which recomputes it from r and gp: k_seg_bwd)
     // o = rms(res + y) s1 [-> rms s2]
@@ -215,7 +221,10 @@ __global__ __launch_bounds__(64, 1) void k_seg_post(SegArgs a) {
 //   dsum = d(res + y)  from  o = rms(rms(res + y) s1) s2   with incoming d0 (+ d1 + d2)          (k_resnorm_bwd)
 //   du   = dsum W_o^T                                                                            (dense layer)
 //   dr, dg from u = swish(g) * GroupNorm(r)                                                      (k_retpost_bwd)
-// plus the four parameter-gradient rows (s1, s2, gamma, beta) as per-wave slabs.  Reads 5-7 rows, writes 3 (was 12-13 streams).
+// plus the four parameter-gradient rows (s1, s2, gamma, beta) as per-wave slabs.  Row streams with y recomputed: a, d0 (+ d1, d2), r, gate in and
+// dsum, dr, dgp out = 7-9 (a and the gate not counted when they come from the class table; y given: one more; was 12-13).
+//   dW_o = u^T dsum  (RECOMP, optional): both operands are in registers for every row, so the weight gradient is accumulated here
+//   per wave (64 x 64 fp32, 16 MFMA accumulators) instead of storing u in the forward and re-reading u and dsum in a k_wgrad launch.
 struct SegBwdArgs {
   long R;
   const float* a; const float* y; const float* s1; const float* s2;
@@ -226,22 +235,53 @@ struct SegBwdArgs {
   float* dsum; float* dr; float* dgp; long lddg;
   float* slab_s1; float* slab_s2; float* slab_ga; float* slab_be;   // [grid][64]
   const int* rows;   // nullable: a and gp are row tables, token row r reads table row rows[r]
+  float* slab_wo;    // nullable (needs wo_t): [grid][64 in][64 out] per-wave partial sums of dW_o = u^T dsum
 };
 
-template <bool RECOMP>
+// Row tile [16 rows][64] of the feature-major layout -> the K-along-rows MFMA operand: for K-step s lane (m, kq) receives
+// x[row 4 kq + s][16 b + m], b = 0..3 (tile_kstep).  Through LDS at pitch 68: the ds_write_b128 of 8 consecutive lanes (rows m .. m + 7, banks 4 m .. 4 m + 3 of 32) and the
+// ds_read_b32 of a 32-lane half (rows s + 4 kq, kq and kq + 1: banks m and 16 + m) are both conflict-free.  One wave: DS ops execute in order.
+constexpr int TSP = 68;
+__device__ __forceinline__ void tile_stage(float* __restrict__ stg, const Row& x, float scale, int m, int kq) {
+  lsync();   // the previous tile's reads of stg are issued
+#pragma unroll
+  for (int g = 0; g < 4; ++g)
+    *reinterpret_cast<float4*>(stg + m * TSP + 16 * g + 4 * kq) =
+        make_float4(x.v[4 * g] * scale, x.v[4 * g + 1] * scale, x.v[4 * g + 2] * scale, x.v[4 * g + 3] * scale);
+  lsync();
+}
+__device__ __forceinline__ void tile_kstep(const float* __restrict__ stg, int s, int m, int kq, float (&t)[4]) {
+#pragma unroll
+  for (int b = 0; b < 4; ++b) t[b] = stg[(4 * kq + s) * TSP + 16 * b + m];
+}
+
+template <bool RECOMP, bool WGRAD = false>
 __global__ __launch_bounds__(64, 1) void k_seg_bwd(SegBwdArgs a) {
+  static_assert(RECOMP || !WGRAD, "dW_o needs the recomputed u");
   const int lane = threadIdx.x, m = lane & 15, kq = lane >> 4;
   const long ntiles = (a.R + 15) >> 4;
-  float4 wo[4][4];
-  __shared__ __align__(16) float wot[RECOMP ? 64 * WSP : 4];   // W_o^T for the recomputed y: in LDS, the register file is full (466 of 512)
-  load_w64(wo, a.wo_nat, m, kq);
+  // RECOMP: both W_o copies (W_o^T for the recomputed y, W_o for du) live in LDS as fragment-major images and the 64 registers the second
+  // one used to take hold the dW_o accumulator; 4 workgroups share a CU, so the kernel's LDS has to stay under 40 KB (it is 37.25 KB).
+  float4 wo[RECOMP ? 1 : 4][4];
+  __shared__ __align__(16) float wot[RECOMP ? 64 * 64 : 4];
+  __shared__ __align__(16) float won[RECOMP ? 64 * 64 : 4];
+  __shared__ __align__(16) float stg[WGRAD ? 16 * TSP : 4];   // staging tile of the dW_o operands: u, then dsum (a second tile would not fit)
+  if constexpr (!RECOMP) load_w64(wo, a.wo_nat, m, kq);
   // The forward's y = u W_o is recomputed here instead of being written there and read here: the kernel streams at the HBM rate with the
   // matrix cores at 0.16, a second 64 x 64 GEMM per row is free, 256 bytes per row on either side are not.  Same instructions on the same
   // operands as k_seg_post (fswish, the fused multiply-adds of the GroupNorm, dense64_reg on W_o^T): the same bits.
   constexpr bool recompute = RECOMP;
   if (recompute) {
-    for (int i = lane; i < 64 * 16; i += 64) *reinterpret_cast<float4*>(&wot[(i >> 4) * WSP + 4 * (i & 15)]) = ld4g(a.wo_t + (i >> 4) * AE + 4 * (i & 15));
+    fill_flds(wot, a.wo_t, lane); fill_flds(won, a.wo_nat, lane);
     __syncthreads();
+  }
+  // (WGRAD is a template argument, not a branch on slab_wo: behind a branch the accumulator is copied, 64 registers, at the top of every tile)
+  f32x4 dwo[WGRAD ? 4 : 1][WGRAD ? 4 : 1];   // [in block bi][out block bo]: element j of lane (m, kq) is dW_o[16 bi + m][16 bo + 4 kq + j]
+  if constexpr (WGRAD) {
+#pragma unroll
+    for (int bi = 0; bi < 4; ++bi)
+#pragma unroll
+      for (int bo = 0; bo < 4; ++bo) dwo[bi][bo] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   // the four per-feature parameter rows: in registers, or (RECOMP: no registers left) in LDS and re-read where a tile uses them -- the
   // opaque offset keeps the compiler from hoisting those reads back out of the tile loop into 64 live registers
@@ -299,12 +339,20 @@ __global__ __launch_bounds__(64, 1) void k_seg_bwd(SegBwdArgs a) {
     for (int j = 0; j < 16; ++j) t.v[j] = r.v[j] * r.v[j];
     const float mu = row_sum(r) * (1.0f / 64.0f), m2 = row_sum(t) * (1.0f / 64.0f);
     const float rstd = rsqrtf(fmaxf(m2 - mu * mu, 0.f) + EPSN);
+    float ut[4][4];
     if (recompute) {
       const Row gam = prow(2, gam_), bet = prow(3, bet_);
       Row u;
 #pragma unroll
       for (int j = 0; j < 16; ++j) u.v[j] = fswish(g.v[j]) * ((r.v[j] - mu) * rstd * gam.v[j] + bet.v[j]);
-      x = row_add(x, dense64_lds(u, wot, m, kq));
+      int woff = 4 * lane;
+      asm volatile("" : "+v"(woff));
+      x = row_add(x, dense64_flds(u, wot, woff));
+      if constexpr (WGRAD) {   // u^T now (16 registers until dsum exists): the one staging tile is reused for dsum
+        tile_stage(stg, u, 1.0f, m, kq);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) tile_kstep(stg, s, m, kq, ut[s]);
+      }
     }
     // ---- residual + RMSNorm(s) backward
 #pragma unroll
@@ -344,7 +392,27 @@ __global__ __launch_bounds__(64, 1) void k_seg_bwd(SegBwdArgs a) {
     for (int j = 0; j < 16; ++j) dsum.v[j] = (d.v[j] - xh1.v[j] * dot1) * rstd1;
     row_store(a.dsum + rw * AE, kq, dsum);
     // ---- du = dsum W_o^T, then GroupNorm + swish gate backward
-    const Row du = dense64_reg(dsum, wo, nullptr, kq);
+    if constexpr (WGRAD) {   // dW_o += u^T dsum over the tile's live rows: A = dsum^T, B = u^T (K = the 16 rows, 4 per MFMA)
+      tile_stage(stg, dsum, live, m, kq);
+      float dt[4][4];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) tile_kstep(stg, s, m, kq, dt[s]);
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int bi = 0; bi < 4; ++bi)
+#pragma unroll
+          for (int bo = 0; bo < 4; ++bo)
+            dwo[bi][bo] = __builtin_amdgcn_mfma_f32_16x16x4f32(dt[s][bo], ut[s][bi], dwo[bi][bo], 0, 0, 0);
+    }
+    Row du;
+    if constexpr (RECOMP) {
+      int woff = 4 * lane;
+      asm volatile("" : "+v"(woff));
+      du = dense64_flds(dsum, won, woff);
+    } else {
+      du = dense64_reg(dsum, wo, nullptr, kq);
+    }
     const Row gam = prow(2, gam_), bet = prow(3, bet_);
     Row xh, gg, dg;
 #pragma unroll
@@ -376,6 +444,14 @@ __global__ __launch_bounds__(64, 1) void k_seg_bwd(SegBwdArgs a) {
     if (a.s2) row_store(a.slab_s2 + (long)blockIdx.x * AE, kq, ds2);
     row_store(a.slab_ga + (long)blockIdx.x * AE, kq, dga);
     row_store(a.slab_be + (long)blockIdx.x * AE, kq, dbe);
+  }
+  if constexpr (WGRAD) {
+    float* sw = a.slab_wo + (long)blockIdx.x * (AE * AE);
+#pragma unroll
+    for (int bi = 0; bi < 4; ++bi)
+#pragma unroll
+      for (int bo = 0; bo < 4; ++bo)
+        st4g(sw + (16 * bi + m) * AE + 16 * bo + 4 * kq, make_float4(dwo[bi][bo][0], dwo[bi][bo][1], dwo[bi][bo][2], dwo[bi][bo][3]));
   }
 }
 
@@ -418,11 +494,13 @@ extern "C" int magpo_seg_post(const int* dims_host, long R, const void* const* p
 // Number of slab rows magpo_seg_bwd writes for R rows (= its grid size).
 extern "C" int magpo_seg_bwd_grid(long R) { const long nt = (R + 15) / 16; return (int)(nt < 1024 ? (nt < 1 ? 1 : nt) : 1024); }
 
-// ptrs_host[20] (device pointers): a y s1 s2 d0 d1 d2 wo_nat r gp gamma beta | dsum dr dgp | slab_s1 slab_s2 slab_ga slab_be | rows
-// (y, s2, d1, d2, slab_s2, rows may be NULL; with rows, a and gp are row tables read through rows[r]); ldg / lddg: row strides of gp / dgp.  Slabs: [magpo_seg_bwd_grid(R)][64].
+// ptrs_host[21 or 22] (device pointers): a y s1 s2 d0 d1 d2 wo_nat r gp gamma beta | dsum dr dgp | slab_s1 slab_s2 slab_ga slab_be | rows | wo_t
+// [| slab_wo]  (y, s2, d1, d2, slab_s2, rows, wo_t, slab_wo may be NULL; with rows, a and gp are row tables read through rows[r]); ldg / lddg: row
+// strides of gp / dgp.  Slabs: [magpo_seg_bwd_grid(R)][64]; slab_wo (needs wo_t): [magpo_seg_bwd_grid(R)][64 * 64], each wave's u^T dsum as [in][out].
 extern "C" int magpo_seg_bwd(long R, long ldg, long lddg, const void* const* p, int nptrs, hipStream_t st) {
   if (R <= 0) return MAGPO_OK;
-  if (nptrs != 21) { set_error("magpo_seg_bwd: pointer table size mismatch"); return MAGPO_EINVAL; }
+  if (nptrs != 21 && nptrs != 22) { set_error("magpo_seg_bwd: pointer table size mismatch"); return MAGPO_EINVAL; }
+  if (nptrs == 22 && p[21] && !p[20]) { set_error("magpo_seg_bwd: the dW_o slab needs wo_t (u is only formed when y is recomputed)"); return MAGPO_EINVAL; }
   SegBwdArgs a;
   a.R = R; a.ldg = ldg; a.lddg = lddg;
   int i = 0;
@@ -433,7 +511,9 @@ extern "C" int magpo_seg_bwd(long R, long ldg, long lddg, const void* const* p, 
   a.slab_s1 = (float*)p[i++]; a.slab_s2 = (float*)p[i++]; a.slab_ga = (float*)p[i++]; a.slab_be = (float*)p[i++];
   a.rows = (const int*)p[i++];
   a.wo_t = (const float*)p[i++];
-  if (a.wo_t) hipLaunchKernelGGL(k_seg_bwd<true>, dim3((unsigned)magpo_seg_bwd_grid(R)), dim3(64), 0, st, a);
+  a.slab_wo = nptrs == 22 ? (float*)p[i++] : nullptr;
+  if (a.slab_wo) hipLaunchKernelGGL((k_seg_bwd<true, true>), dim3((unsigned)magpo_seg_bwd_grid(R)), dim3(64), 0, st, a);
+  else if (a.wo_t) hipLaunchKernelGGL(k_seg_bwd<true>, dim3((unsigned)magpo_seg_bwd_grid(R)), dim3(64), 0, st, a);
   else hipLaunchKernelGGL(k_seg_bwd<false>, dim3((unsigned)magpo_seg_bwd_grid(R)), dim3(64), 0, st, a);
   return check_launch("magpo_seg_bwd");
 }

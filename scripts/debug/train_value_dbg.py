@@ -39,8 +39,11 @@ out, _, ret = onets.msr_chunk(p, "enc.block0.retn.", xn, xn, xn, h0, dones, pos,
 rep_err("r0", b["t_r0"], ret)
 rn = onets.groupnorm_rows(ret.reshape(-1, 64), p["enc.block0.retn.gn.scale"], p["enc.block0.retn.gn.bias"], 1).reshape(ret.shape)
 u = onets.swish(kin @ p["enc.block0.retn.w_g"]) * rn
-rep_err("u0", b["t_u0"], u)
-rep_err("y0", b["t_y0"], out)
+for name, ref in (("u0", u), ("y0", out)):   # only the unfused segment path stores them (the fused backward recomputes both)
+    if "t_" + name in b:
+        rep_err(name, b["t_" + name], ref)
+    else:
+        print(f"{name:8s} not stored on this path")
 x1 = onets.rmsnorm(xn + out, p["enc.block0.ln1.scale"]); rep = onets.rmsnorm(x1, p["enc.block0.ln2.scale"])
 rep_err("rep", b["t_rep"], rep)
 rep_err("value", b["t_value"], onets._value_head(p, rep))
