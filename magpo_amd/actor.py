@@ -9,38 +9,33 @@ training forward and the hand-derived BPTT backward.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Optional
 
 import contextlib
 
 import numpy as np
 import torch
 
-from ._lib import lib
-from .params import FlatParams, actor_layout, actor_named_views, init_actor
-from .sable import _Bufs
+from .netbase import NetBase
+from .params import FlatParams, actor_layout, actor_named_views, init_actor, init_actor_from_key
 from .torso import DEFAULT_TORSO, TorsoSpec, layer_name
 from .tuning import Tuning
 
 H = 128
 
 
-class GruActor:
+class GruActor(NetBase):
+    LINEAR_VARIANT = "actor_linear_variant"
+
     def __init__(self, n_agents: int, action_dim: int, obs_dim: int, device, *, hidden: int = 128, wgrad_groups: int = 512,
                  seed: Optional[int] = None, grads: Optional[torch.Tensor] = None, tuning: Optional[Tuning] = None, obs_ld: Optional[int] = None,
                  pre_torso: Optional[TorsoSpec] = None, post_torso: Optional[TorsoSpec] = None):
-        self.tuning = tuning if tuning is not None else Tuning.from_env()   # per-call kernel knobs (tuning.py); the library keeps none
         if hidden != 128:
             raise NotImplementedError("gfx950 GRU kernels: hidden_state_dim = 128 only")
         if obs_dim > 128 or action_dim > 32:
             raise NotImplementedError("obs_dim <= 128 and action_dim <= 32 required")
-        self.A, self.K, self.F = n_agents, action_dim, obs_dim
-        self.wide = obs_dim > 32            # wide observations: rows padded to 128, pre-torso on the MFMA dense kernel (csrc/wideobs.hip)
-        self.Fld = 128 if self.wide else obs_dim      # floats between observation rows
-        if obs_ld is not None and int(obs_ld) != self.Fld:   # rows wider than the features read (system.add_agent_id: False, envs.net_obs)
-            if self.wide or int(obs_ld) < obs_dim:
-                raise ValueError(f"obs_ld={obs_ld} with obs_dim={obs_dim}: a separate row stride is supported for narrow observations only")
-            self.Fld = int(obs_ld)
+        super().__init__(obs_dim, device, wgrad_groups, tuning, obs_ld)   # (wide observations: the pre-torso runs on the MFMA dense kernel)
+        self.A, self.K = n_agents, action_dim
         self.pre_spec = pre_torso if pre_torso is not None else DEFAULT_TORSO
         self.post_spec = post_torso if post_torso is not None else DEFAULT_TORSO
         self.Dpre, self.Dpost = self.pre_spec.width, self.post_spec.width
@@ -49,9 +44,6 @@ class GruActor:
         p0 = self.pre_spec
         self.small_first = not self.wide and p0.layer_sizes[0] == 128 and p0.act(0) == 1 and not p0.use_layer_norm
         self.KP = 128 if self.wide else 64    # columns of the first layer's (padded) operand
-        self.dev = device
-        self.L = lib()
-        self.G = wgrad_groups
         self.P = FlatParams(actor_layout(obs_dim, H, action_dim, self.pre_spec, self.post_spec), device)
         self.grads = torch.zeros_like(self.P.flat) if grads is None else grads
         assert self.grads.numel() == self.P.numel
@@ -60,14 +52,9 @@ class GruActor:
         self.named = actor_named_views(self.v)
         self.named_grads = actor_named_views(self.gv)
         if isinstance(seed, np.ndarray):   # a PRNG key: the parameters flax creates from it (rec_magpo.py:623; params.init_actor_from_key)
-            from .params import init_actor_from_key
             init_actor_from_key(self.named, seed)
         elif seed is not None:
             init_actor(self.named, seed)
-        self.wt: Dict[str, torch.Tensor] = {}
-        self.b = _Bufs(device)
-        self.wgrad_stream = torch.cuda.Stream(device=device) if torch.device(device).type == "cuda" else None
-        self.overlap_wgrad = False  # opt-in (bench.py --overlap): ~0.5 %, but per-kernel timings then include contention
         shapes = [(H, 3 * H), (self.Dpre, 3 * H), (self.Dpost, self.K)]   # every (KIN, NOUT) of a weight gradient
         for spec, din in ((self.pre_spec, self.KP), (self.post_spec, H)):
             for d in spec.layer_sizes:
@@ -75,9 +62,6 @@ class GruActor:
                 din = d
         self.wg_ws = torch.empty(max(self.L.call("magpo_wgrad_workspace_floats", k, n, self.G) for k, n in shapes), device=device)
         self.refresh()
-
-    def _st(self):
-        return torch.cuda.current_stream().cuda_stream
 
     def bind_grads(self, grads: torch.Tensor) -> None:
         """Make ``grads`` (flat, P.numel floats, e.g. a slice of the learner's all-reduce message) the gradient buffer."""
@@ -91,16 +75,6 @@ class GruActor:
             for n, v in self.named.items():
                 v.copy_(params[n].to(self.dev, torch.float32).reshape(v.shape))
         self.refresh()
-
-    def _tp(self, name, W, npad=None):
-        K_, N_ = W.shape
-        npad = npad or (N_ + 31) // 32 * 32
-        t = self.wt.get(name)
-        if t is None:
-            t = torch.zeros(npad, K_, device=self.dev)
-            self.wt[name] = t
-        self.L.call("magpo_transpose_pad", W, t, K_, N_, npad, self._st())
-        return t
 
     def refresh(self):
         v = self.v
@@ -129,9 +103,6 @@ class GruActor:
         else:
             L.call("magpo_copy_rows", src, 3 * H, dst[:, 2 * H:], 3 * H, rows, H, st)
             L.call("magpo_copy_rows", src[:, H:], 3 * H, dst, 3 * H, rows, 2 * H, st)
-
-    def lin(self, X, ldx, Wt, bias, Y, ldy, R, KIN, NOUT, act=0, Ypre=None):
-        self.L.call("magpo_linear", X, ldx, Wt, bias, Y, ldy, Ypre, R, KIN, NOUT, act, self.tuning.actor_linear_variant, self._st())
 
     def _torso_fwd(self, prefix, spec, X, ldx, R, ctx):
         """One MLPTorso (torsos.py:36-47) on R rows of X (stride ldx; the pre-torso's X are observation rows of F features).  Buffers are
@@ -193,7 +164,7 @@ class GruActor:
                 grid = L.call("magpo_row_grid", R)
                 slab = b.get(f"g_{prefix}{i}.slab", (grid, d))
                 L.call("magpo_ln_act_bwd", dy, d, y, d, ln[0], d, ln[1], dz, d, slab, R, d, spec.act(i), st)
-                L.call("magpo_reduce_slabs", slab, gv[n + ".ln.bias"], grid, d, d, 1.0, 0, st)
+                self.reduce(slab, gv[n + ".ln.bias"])
             else:
                 dz = dy
             krows = self.F if (prefix == "pre" and i == 0) else None
@@ -212,24 +183,10 @@ class GruActor:
             act, M = (4 if spec.act(j) == 1 else 6), rec[3]
         self.lin(dsrc, ldsrc, W_nat, None, dst, NOUT, R, KIN, NOUT, act=act, Ypre=M)
 
-    def _groups(self, R):
-        """Row slabs of a split weight gradient: no more than one per 256 rows (small minibatches: fewer partials to reduce)."""
-        return max(1, min(self.G, R // 256))
-
-    def wgrad(self, X, ldx, dY, ldy, R, KIN, NOUT, dW, db=None, krows=None):
-        """dW = X^T dY, queued on the side stream (off the critical path of the backward chain)."""
-        side = self.wgrad_stream if self.overlap_wgrad else None
-        if side is None:
-            self.L.call("magpo_wgrad", X, ldx, dY, ldy, R, KIN, krows or KIN, NOUT, dW, db, self.wg_ws, self._groups(R), 1.0, 0, self.tuning.wgrad_variant, self._st())
-            return
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self.L.call("magpo_wgrad", X, ldx, dY, ldy, R, KIN, krows or KIN, NOUT, dW, db, self.wg_ws, self._groups(R), 1.0, 0, self.tuning.wgrad_variant, self._st())
-
     def _wgrad_nrz(self, emb, dg, R, gw, dW, db):
         """dW_i, db_i from dg's columns 0..3H (gate blocks n | r | z) into W_i's order, on the weight-gradient stream."""
         D = self.Dpre
-        side = self.wgrad_stream if self.overlap_wgrad else None
+        side = self._wgrad_side()
         if side is not None:
             side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
@@ -323,7 +280,7 @@ class GruActor:
         nblk = (nseq * A + 63) // 64
         slab = b.get("g_slab", (nblk, H))
         L.call("magpo_gru_scan_bwd", b.t["t_gates"], b.t["t_hprev"], dones, dhs, v["gru.wh"], dg, slab, nseq, T, A, self.tuning.gru_split_bf16, self.tuning.gru_block_rows, st)
-        L.call("magpo_reduce_slabs", slab, gv["gru.hn.bias"], nblk, H, H, 1.0, 0, st)
+        self.reduce(slab, gv["gru.hn.bias"])
         self.wgrad(b.t["t_hprev"], H, dg[:, H:], 4 * H, R, H, 3 * H, gv["gru.wh"])
         if sv["classes"] is not None:
             # input side on the class table: S[c] = sum of the rows of class c, gate blocks back into W_i's order on the C rows, then the
@@ -356,10 +313,9 @@ class GruActor:
             grid = L.call("magpo_row_grid", R)
             sw = b.get("g_slabw", (grid, 33 * H))
             L.call("magpo_small_relu_wgrad", obs, self.Fld, F, emb0, d0, sw, R, st)
-            L.call("magpo_reduce_slabs", sw, gv["pre.kernel"], grid, F * H, 33 * H, 1.0, 0, st)
-            L.call("magpo_reduce_slabs", sw[:, 32 * H:], gv["pre.bias"], grid, H, 33 * H, 1.0, 0, st)
-        if self.overlap_wgrad and self.wgrad_stream is not None:
-            torch.cuda.current_stream().wait_stream(self.wgrad_stream)
+            self.reduce(sw, gv["pre.kernel"], P=F * H, stride=33 * H)
+            self.reduce(sw[:, 32 * H:], gv["pre.bias"], P=H, stride=33 * H)
+        self._join_wgrad()
 
 
 GruActor.apply = GruActor.seq_fwd   # actor_network.apply (rec_magpo.py:631): the scanned training forward (its backward: seq_bwd)

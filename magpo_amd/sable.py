@@ -23,8 +23,8 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from ._lib import lib
-from .params import FlatParams, WidthEmbedding, guider_layout, guider_named_views, init_guider
+from .netbase import NetBase, _Bufs  # noqa: F401  (_Bufs stays importable from this module)
+from .params import FlatParams, WidthEmbedding, guider_layout, guider_named_views, init_guider, init_guider_from_key
 from .tuning import Tuning
 
 E = 64      # width of the fused (64-wide) kernel family, of a retention state tile and of a logit row
@@ -38,25 +38,11 @@ def decay_kappas(n_head: int, scaling: float):
     return [float(x) for x in (k.astype(np.float32) * np.float32(scaling)).astype(np.float32)]
 
 
-class _Bufs:
-    def __init__(self, device):
-        self.device = device
-        self.t: Dict[str, torch.Tensor] = {}
-
-    def get(self, name, shape, dtype=torch.float32, zero=False):
-        t = self.t.get(name)
-        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
-            t = (torch.zeros if zero else torch.empty)(*shape, dtype=dtype, device=self.device)
-            self.t[name] = t
-        return t
-
-
-class SableGuider:
+class SableGuider(NetBase):
     def __init__(self, n_agents: int, action_dim: int, obs_dim: int, device, *, embed_dim: int = 64, n_head: int = 1,
                  n_block: int = 1, decay_scaling_factor: float = 0.8, use_pe: bool = True, max_pos: int = 101,
                  wgrad_groups: int = 512, seed: Optional[int] = None, grads: Optional[torch.Tensor] = None,
                  tuning: Optional[Tuning] = None, obs_ld: Optional[int] = None):
-        self.tuning = tuning if tuning is not None else Tuning.from_env()   # per-call kernel knobs (tuning.py); the library keeps none
         if embed_dim not in (16, 32, 64, 128) or n_head not in (1, 2, 4) or n_block < 1 or embed_dim % n_head or 64 // n_head // n_head < 4:
             raise NotImplementedError("gfx950 Sable kernels: embed_dim in {16, 32, 64, 128} (nets narrower than 64 run embedded in the 64-wide "
                                       "kernels, params.WidthEmbedding) and n_head in {1, 2, 4} (SURVEY 8f rank 3)")
@@ -70,20 +56,10 @@ class SableGuider:
         self.ntile = 4 if self.blockwise else self.nh
         if obs_dim > 128 or action_dim > 31:
             raise NotImplementedError("obs_dim <= 128 and action_dim <= 31 required")
-        self.A, self.K, self.F = n_agents, action_dim, obs_dim
-        # observation rows: F floats apart for small observations (row kernels), padded to 128 for wide ones (obs_dim > 32, e.g.
-        # Robot Warehouse: the observation-side first layer then runs on the MFMA dense kernels, csrc/wideobs.hip)
-        self.wide = obs_dim > 32
-        self.Fld = 128 if self.wide else obs_dim      # floats between observation rows
-        if obs_ld is not None and int(obs_ld) != self.Fld:   # rows wider than the features read (system.add_agent_id: False, envs.net_obs)
-            if self.wide or int(obs_ld) < obs_dim:
-                raise ValueError(f"obs_ld={obs_ld} with obs_dim={obs_dim}: a separate row stride is supported for narrow observations only")
-            self.Fld = int(obs_ld)
-        self.dev = device
-        self.L = lib()
+        super().__init__(obs_dim, device, wgrad_groups, tuning, obs_ld)
+        self.A, self.K = n_agents, action_dim
         self.kappas = decay_kappas(self.nh, decay_scaling_factor)
         self.kappa = self.kappas[0]
-        self.G = wgrad_groups
         # P / grads: the LOGICAL parameters (optimiser, all-reduce, checkpoints); PD / grads_D: what the kernels read and write.
         # For embed_dim = 64 they are the same buffers.
         self.P = FlatParams(guider_layout(self.EL, obs_dim, action_dim, self.nb, self.nh), device)
@@ -100,7 +76,6 @@ class SableGuider:
         self.named = guider_named_views(self.P.views(), self.EL, self.nh)
         self.named_grads = guider_named_views(self.P.views(self.grads), self.EL, self.nh)
         if isinstance(seed, np.ndarray):   # a PRNG key: the parameters flax creates from it (rec_magpo.py:598-604; params.init_guider_from_key)
-            from .params import init_guider_from_key
             init_guider_from_key(self.named, seed, self.EL, self.nh)
         elif seed is not None:
             init_guider(self.named, seed, self.EL)
@@ -113,23 +88,12 @@ class SableGuider:
                 pe_l = torch.zeros(max_pos, self.EL, device=device)
                 self.L.call("magpo_pe_table", pe_l, max_pos, self.EL, self._st())
                 self.pe.copy_(self.emb.expand_rows(pe_l))
-        self.wt: Dict[str, torch.Tensor] = {}
-        self.wa: Dict[str, torch.Tensor] = {}   # fragment-major copies for the fused acting kernel (build_act_weights)
-        self._act_w_dirty = True
-        self.b = _Bufs(device)
-        self._act_tabs: Dict[tuple, tuple] = {}
-        self._seg_tabs: Dict[tuple, tuple] = {}
+        self.wa: Dict[str, torch.Tensor] = {}   # fragment-major copies of self.wt for the fused acting kernel: refresh() keeps both current
         self.fused_segments = self.nh == 1 and E == 64   # token-local parts between retention ops as single launches (csrc/seg_fused.hip)
-        # weight-gradient GEMMs run on a side stream: they are off the critical path of the backward chain
-        self.wgrad_stream = torch.cuda.Stream(device=device) if torch.device(device).type == "cuda" else None
-        self.overlap_wgrad = False  # opt-in (bench.py --overlap): ~0.5 %, but per-kernel timings then include contention
         self.wg_ws = torch.empty(self.L.call("magpo_wgrad_workspace_floats", E, 4 * E, self.G), device=device)
         self.refresh()
 
     # ------------------------------------------------------------------ plumbing
-    def _st(self):
-        return torch.cuda.current_stream().cuda_stream
-
     def bind_grads(self, grads: torch.Tensor) -> None:
         """Make ``grads`` (a flat fp32 buffer of P.numel floats, e.g. a slice of the learner's all-reduce message) the gradient buffer."""
         assert grads.numel() == self.P.numel
@@ -151,18 +115,10 @@ class SableGuider:
         self.check_ffn_zero()
         self.refresh()
 
-    def _tp(self, name, W, npad=None):
-        K_, N_ = W.shape
-        npad = npad or (N_ + 31) // 32 * 32
-        t = self.wt.get(name)
-        if t is None:
-            t = torch.zeros(npad, K_, device=self.dev)
-            self.wt[name] = t
-        self.L.call("magpo_transpose_pad", W, t, K_, N_, npad, self._st())
-        return t
-
     def refresh(self):
-        """Rebuild the device parameters (embed_dim < 64) and the transposed (forward-GEMM) weight copies after a parameter update."""
+        """Rebuild the device parameters (embed_dim < 64), the transposed (forward-GEMM) weight copies and the acting kernel's
+        fragment-major copies of those after a parameter update.  Every copy is written in place on the calling stream, so work queued
+        behind it -- a captured rollout included -- reads the new weights and never writes them."""
         if self.emb is not None:
             self.emb.expand(self.P.flat, self.PD.flat)
         v, E = self.v, self.E
@@ -191,7 +147,7 @@ class SableGuider:
                         if key not in self.wt:
                             self.wt[key] = torch.empty(E, 2 * E, device=self.dev)
                         self.wt[key].copy_(W[:, half * 2 * E:(half + 1) * 2 * E])
-        self._act_w_dirty = True   # the acting kernel's fragment-major copies are rebuilt before the next acting step (build_act_weights)
+        self.build_act_weights()
 
     def _act_weight_names(self):
         names = ["vh0", "h0", "h1"]
@@ -202,8 +158,8 @@ class SableGuider:
     def build_act_weights(self):
         """Fragment-major copies of the transposed weights for the fused acting kernel (csrc/fm_rows.hpp: wfrag<true>):
         Wf[g][gk][lane = m + 16 kq][4] = Wt[16 g + m][16 gk + 4 kq .. + 3], so that a wave's weight-fragment load is 1 KB contiguous.
-        In-place copies into persistent buffers (static pointers: safe inside a HIP-graph capture); the rollout calls this at its start
-        (MagpoLearner._rollout_body), a stand-alone ``act_fused`` when the parameters changed since the last build."""
+        In-place copies into persistent buffers (static pointers for the captured rollouts, which only read them); the last step of
+        :meth:`refresh`, so they exist from construction on and change whenever the transposed copies do."""
         if self.E != 64:
             return
         for name in self._act_weight_names():
@@ -212,29 +168,10 @@ class SableGuider:
             if d is None:
                 d = self.wa[name] = torch.empty_like(t)
             self.L.call("magpo_act_weight_layout", t, d, t.shape[0], self._st())
-        self._act_w_dirty = False
 
-    def lin(self, X, ldx, Wt, bias, Y, ldy, R, KIN, NOUT, act=0, Ypre=None):
-        self.L.call("magpo_linear", X, ldx, Wt, bias, Y, ldy, Ypre, R, KIN, NOUT, act, self.tuning.linear_variant, self._st())
-
-    def _groups(self, R):
-        """Row slabs of a split weight gradient: no more than one per 256 rows (small minibatches: fewer partials to reduce)."""
-        return max(1, min(self.G, R // 256))
-
-    def wgrad(self, X, ldx, dY, ldy, R, KIN, NOUT, dW, db=None, krows=None):
-        """dW = X^T dY.  With overlap_wgrad the GEMM is queued on the side stream behind everything the calling stream
-        has queued so far (so X and dY are complete); the caller must not overwrite dY before train_bwd joins."""
+    def _wgrad_side(self):
         # (with n_block > 1 the d(obs_rep) sums are accumulated in place, so the side stream is not used)
-        side = self.wgrad_stream if (self.overlap_wgrad and self.nb == 1) else None
-        if side is None:
-            self.L.call("magpo_wgrad", X, ldx, dY, ldy, R, KIN, krows or KIN, NOUT, dW, db, self.wg_ws, self._groups(R), 1.0, 0, self.tuning.wgrad_variant, self._st())
-            return
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self.L.call("magpo_wgrad", X, ldx, dY, ldy, R, KIN, krows or KIN, NOUT, dW, db, self.wg_ws, self._groups(R), 1.0, 0, self.tuning.wgrad_variant, self._st())
-
-    def reduce(self, slab, out, P=None, stride=None, accumulate=False):
-        self.L.call("magpo_reduce_slabs", slab, out, slab.shape[0], P or slab.shape[1], stride or slab.shape[1], 1.0, 1 if accumulate else 0, self._st())
+        return super()._wgrad_side() if self.nb == 1 else None
 
     def lin_dx_qkvg(self, dY, name, dX, R):
         """dX [R, E] = dY [R, 4E] W^T for a fused q|k|v|g projection ``name`` ([E, 4E]): one launch up to KIN = 256, two K-halves + add for E = 128."""
@@ -353,18 +290,6 @@ class SableGuider:
             if not v_first:
                 self.add_rows(dv[:, ov:], lddv, tv, TILE, R, TILE)
 
-    def _retpost_fwd(self, r, gp, ldg, gamma, beta, u, R):
-        E = self.E
-        self.L.call("magpo_retpost_fwd", r, E, gp, ldg, gamma, beta, u, E, R, self.hs, self.gs, E, self._st())
-
-    def _retpost_bwd(self, r, gp, ldg, pfx, du, dr, dgp, lddg, R, sa, sb):
-        v, gv, E = self.v, self.gv, self.E
-        self.L.call("magpo_retpost_bwd", r, E, gp, ldg, v[pfx + "gn.scale"], v[pfx + "gn.bias"], du, E, dr, E, dgp, lddg, sa, sb, R,
-                    self.hs, self.gs, E, self._st())
-        for h in range(self.nh):   # scale / bias [hs] are shared by the heads: fold the per-column slabs
-            self.reduce(sa[:, h * self.hs:], gv[pfx + "gn.scale"], P=self.hs, stride=E, accumulate=h > 0)
-            self.reduce(sb[:, h * self.hs:], gv[pfx + "gn.bias"], P=self.hs, stride=E, accumulate=h > 0)
-
     def act(self, obs, pos, states, sample_keys, action_out, logp_out, value_out, mask=None, value_only=False):
         """One env step for N envs (SableNetwork.get_actions, sable_network.py:443-482).  obs [N,A,F] f32, pos [N] i32
         (step_count), states = (S_enc, S_d1, S_d2) each [n_block, N, 64, 64] updated in place, sample_keys = [A,2]
@@ -473,19 +398,11 @@ class SableGuider:
         v, b = self.v, self.b
         s_enc, s_d1, s_d2 = states   # value_only (bootstrap value, rec_magpo.py:202-208): the kernel writes no state
         kdev = sample_keys if torch.is_tensor(sample_keys) else None
-        cache_key = (N, bool(value_only), bool(pending), bool(flush), bool(precand), bool(defer), self.tuning.act_envs_per_wave, obs.data_ptr(), pos.data_ptr(), None if mask is None else mask.data_ptr(),
-                     None if kdev is None else kdev.data_ptr(), s_enc.data_ptr(), s_d1.data_ptr(), s_d2.data_ptr(),
-                     None if action_out is None else action_out.data_ptr(), None if logp_out is None else logp_out.data_ptr(),
-                     value_out.data_ptr(), None if done is None else done.data_ptr())
-        if self._act_w_dirty and not torch.cuda.is_current_stream_capturing():
-            self.build_act_weights()   # (a captured rollout rebuilds them itself, as graph nodes: MagpoLearner._rollout_body)
-        tabs = self._act_tabs.get(cache_key)
-        if tabs is None:
-            if not self.wa:
-                self.build_act_weights()
+        args = (obs, pos, mask, kdev, s_enc, s_d1, s_d2, action_out, logp_out, value_out, done)
+
+        def table():   # the global pointers, then 21 per block (everything beside ``args``: parameters, weight copies, scratch of (tag, N))
             wa = self.wa
             g = lambda n, w=E, rows=R: b.get(f"f{tag}_" + n, (rows, w))   # scratch per caller tag (env groups may act concurrently)
-            ptr = lambda t: 0 if t is None else t.data_ptr()
             glob = [obs, pos, mask, kdev,
                     v["enc.obs.norm.scale"], v["enc.obs.dense.kernel"], v["enc.ln.scale"], v["dec.act.kernel"], v["dec.ln.scale"],
                     wa["vh0"], v["enc.head.dense0.bias"], v["enc.head.norm.scale"], v["enc.head.dense1.kernel"], v["enc.head.dense1.bias"],
@@ -504,14 +421,13 @@ class SableGuider:
                         wa[f"q2{k}"], wa[f"kvg2{k}"], wa[f"wo2{k}"], v[d + "ln2.scale"], v[d + "ln3.scale"],
                         v[d + "retn2.gn.scale"], v[d + "retn2.gn.bias"],
                         g(f"qkvg1_{k}", 4 * E), g(f"q2_{k}"), g(f"kvg2_{k}", 4 * E)]   # kvg2 rows: [k | v | - | P2] (ld 256)
-            tabs = (np.array([N, A, K, F, nb, nh, self.hs, self.gs, self.npos, 1 if value_only else 0, self.Fld, self.tuning.act_envs_per_wave,
-                              1 if pending else 0, 1 if flush else 0, 1 if precand else 0, 1 if defer else 0], dtype=np.int32),
-                    np.array((self.kappas + [0.0] * 4)[:4], dtype=np.float32),
-                    np.array([ptr(t) for t in glob], dtype=np.uint64), np.array([ptr(t) for t in blk], dtype=np.uint64))
-            if len(self._act_tabs) > 4096:
-                self._act_tabs.clear()
-            self._act_tabs[cache_key] = tabs
-        dims, kap, gp, bp = tabs
+            return glob + blk
+
+        tab = self.ptr_table(("act", tag, N) + tuple(None if t is None else t.data_ptr() for t in args), table)
+        gp, bp = tab[:tab.size - 21 * nb], tab[tab.size - 21 * nb:]
+        dims = np.array([N, A, K, F, nb, nh, self.hs, self.gs, self.npos, 1 if value_only else 0, self.Fld, self.tuning.act_envs_per_wave,
+                         1 if pending else 0, 1 if flush else 0, 1 if precand else 0, 1 if defer else 0], dtype=np.int32)
+        kap = np.array((self.kappas + [0.0] * 4)[:4], dtype=np.float32)
         keys = None
         if kdev is None and not value_only:
             keys = np.ascontiguousarray(np.asarray(sample_keys, dtype=np.uint32).reshape(A, 2))
@@ -521,47 +437,95 @@ class SableGuider:
     # the reference's names for the two apply functions of the Sable network (rec_magpo.py:624-628)
     get_actions = act_fused          # partial(sable_network.apply, method="get_actions"): execution  (apply = train_fwd: end of the file)
 
-    def _seg_post(self, tail, r, gp, ldg, gamma, beta, wo_t, res, s1, s2, pos, u, y, o, ope, R, w0_t=None, b0=None, out0=None, ld0=0,
-                  hs=None, hw=None, hb1=None, value=None, q2_t=(), q2=(), hn=None, w1_t=None, b1=None, logits=None, rows=None):
-        """One fused launch for the token-local part between two retention ops (csrc/seg_fused.hip)."""
-        ptr = lambda t: 0 if t is None else t.data_ptr()
-        q2_t, q2 = list(q2_t) + [None] * (4 - len(q2_t)), list(q2) + [None] * (4 - len(q2))
-        tab = [r, gp, gamma, beta, wo_t, res, s1, s2, self.pe, pos, u, y, o, ope, w0_t, b0, out0, hs, hw, hb1, value, *q2_t, *q2, hn, w1_t, b1, logits, rows]
-        key = (tail, R, tuple(ptr(t) for t in tab))
-        ent = self._seg_tabs.get(key)
-        if ent is None:
-            nq2 = sum(1 for t in q2 if t is not None)
-            ent = (np.array([tail, self.K, self.npos, ldg, ld0, nq2], dtype=np.int32), np.array([ptr(t) for t in tab], dtype=np.uint64))
-            if len(self._seg_tabs) > 256:
-                self._seg_tabs.clear()
-            self._seg_tabs[key] = ent
-        self.L.call("magpo_seg_post", ent[0].ctypes.data, R, ent[1].ctypes.data, int(ent[1].size), self._st())
+    # ------------------------------------------------------------------ post-retention segment (contract of magpo_seg_post / magpo_seg_bwd)
+    def _seg_fwd(self, tail, key, pfx, r, gp, ldg, res, s1, s2, pos, o, ope, R, w0_t=None, b0=None, out0=None, ld0=0, hs=None, hw=None,
+                 hb1=None, value=None, q2_t=(), q2=(), hn=None, w1_t=None, b1=None, logits=None, rows=None):
+        """Token-local part between two retention ops, for the retention layer ``pfx`` (parameters) / ``key`` (W_o^T copy, workspaces):
+        u = swish(gp) * GroupNorm(r); y = u W_o; o = rms(res + y) s1 [-> rms s2]; ope = o + pe[pos]; then the tail (include/magpo.h:
+        1 value head + cross-retention queries, 2 the k | v | g projection, 3 logit head, 0 none).  One launch (csrc/seg_fused.hip)
+        with ``fused_segments`` -- u and y are then not stored: the fused backward recomputes them -- else kernel by kernel."""
+        v, E = self.v, self.E
+        gamma, beta, wo_t = v[pfx + "gn.scale"], v[pfx + "gn.bias"], self.wt["wo" + key]
+        if self.fused_segments:
+            q2_t, q2 = list(q2_t) + [None] * (4 - len(q2_t)), list(q2) + [None] * (4 - len(q2))
+            tab = [r, gp, gamma, beta, wo_t, res, s1, s2, self.pe, pos, None, None, o, ope, w0_t, b0, out0, hs, hw, hb1, value, *q2_t, *q2,
+                   hn, w1_t, b1, logits, rows]
+            ptrs = self.ptr_table(("seg_post",) + tuple(None if t is None else t.data_ptr() for t in tab), tab)
+            dims = np.array([tail, self.K, self.npos, ldg, ld0, sum(1 for t in q2 if t is not None)], dtype=np.int32)
+            self.L.call("magpo_seg_post", dims.ctypes.data, R, ptrs.ctypes.data, int(ptrs.size), self._st())
+            return
+        assert rows is None, "class tables are read in place by the fused segment kernels only"
+        L, st = self.L, self._st()
+        u, y = self.b.get("t_u" + key, (R, E)), self.b.get("t_y" + key, (R, E))   # kept for the backward
+        L.call("magpo_retpost_fwd", r, E, gp, ldg, gamma, beta, u, E, R, self.hs, self.gs, E, st)
+        self.lin(u, E, wo_t, None, y, E, R, E, E)
+        pe = (self.pe, pos, 1, self.npos) if ope is not None else (None, None, 0, 0)
+        L.call("magpo_resnorm_fwd", res, E, y, E, s1, s2, *pe, o, 0 if o is None else E, ope, 0 if ope is None else E, R, E, st)
+        if tail == 2:
+            self.lin(ope, E, w0_t, b0, out0, ld0, R, E, ld0)
+        elif tail:
+            self.lin(o, E, w0_t, b0, out0, ld0, R, E, E)
+            if tail == 1:
+                L.call("magpo_headmid_fwd", out0, ld0, hs, None, 0, hw, hb1, value, 1, R, E, st)
+                for wq, q in zip(q2_t, q2):
+                    self.lin(ope, E, wq, None, q, E, R, E, E)
+            else:
+                L.call("magpo_headmid_fwd", out0, ld0, hs, hn, E, None, None, None, 0, R, E, st)
+                self.lin(hn, E, w1_t, b1, logits, LW, R, E, self.K)
 
-    def _seg_bwd(self, a, y, s1, s2, d0, d1, d2, wo_nat, r, gp, ldg, pfx, dsum, dr, dgp, lddg, R, g_s1, g_s2, acc_s1=False, rows=None, wo_t=None,
-                 g_wo=None):
-        """Backward of the front of a post-retention segment in one launch (csrc/seg_fused.hip: k_seg_bwd): d(res + y) through the
-        RMSNorm(s), dsum W_o^T, GroupNorm + gate backward, and the four parameter-gradient rows (reduced from per-wave slabs).
-        ``g_wo`` (needs ``wo_t``): the W_o gradient u^T dsum comes out of the same launch, from the u the kernel recomputes."""
-        v, gv, b = self.v, self.gv, self.b
-        ptr = lambda t: 0 if t is None else t.data_ptr()
-        G = self.L.call("magpo_seg_bwd_grid", R)
-        sl = [b.get(f"sb_{i}", (G, E)) for i in range(4)]
-        tab = [a, y, s1, s2, d0, d1, d2, wo_nat, r, gp, v[pfx + "gn.scale"], v[pfx + "gn.bias"], dsum, dr, dgp, sl[0], sl[1] if s2 is not None else None, sl[2], sl[3], rows, wo_t]
-        if g_wo is not None:
+    def _seg_bwd(self, key, pfx, a, s1, s2, d0, d1, d2, r, gp, ldg, dsum, dr, dgp, lddg, R, g_s1, g_s2, rows=None):
+        """Backward of the front of :meth:`_seg_fwd` (a = its ``res``): dsum = d(res + y) of the incoming d0 [+ d1 + d2] through the
+        RMSNorm(s), the W_o gradient u^T dsum, du = dsum W_o^T, (dr, dgp) through GroupNorm + gate, and the parameter-gradient rows of
+        s1 [, s2], gamma, beta.  One launch + slab reductions (csrc/seg_fused.hip: k_seg_bwd) with ``fused_segments``, else kernel
+        by kernel on the u and y the composed forward kept."""
+        v, gv, b, E = self.v, self.gv, self.b, self.E
+        gamma, beta, wo_nat, g_wo = v[pfx + "gn.scale"], v[pfx + "gn.bias"], v[pfx + "w_o"], gv[pfx + "w_o"]
+        if self.fused_segments:
+            G = self.L.call("magpo_seg_bwd_grid", R)
+            sl = [b.get(f"sb_{i}", (G, E)) for i in range(4)]
             sl_wo = b.get("sb_wo", (G, E * E))
-            tab.append(sl_wo)
-        key = ("bwd", R, ldg, lddg, tuple(ptr(t) for t in tab))
-        ent = self._seg_tabs.get(key)
-        if ent is None:
-            ent = np.array([ptr(t) for t in tab], dtype=np.uint64)
-            self._seg_tabs[key] = ent
-        self.L.call("magpo_seg_bwd", R, ldg, lddg, ent.ctypes.data, int(ent.size), self._st())
-        self.reduce(sl[0], g_s1, accumulate=acc_s1)
-        if s2 is not None:
-            self.reduce(sl[1], g_s2)
-        self.reduce(sl[2], gv[pfx + "gn.scale"]); self.reduce(sl[3], gv[pfx + "gn.bias"])
-        if g_wo is not None:
+            tab = [a, None, s1, s2, d0, d1, d2, wo_nat, r, gp, gamma, beta, dsum, dr, dgp, sl[0], sl[1] if s2 is not None else None, sl[2], sl[3],
+                   rows, self.wt["wo" + key], sl_wo]
+            ptrs = self.ptr_table(("seg_bwd",) + tuple(None if t is None else t.data_ptr() for t in tab), tab)
+            self.L.call("magpo_seg_bwd", R, ldg, lddg, ptrs.ctypes.data, int(ptrs.size), self._st())
+            self.reduce(sl[0], g_s1)
+            if s2 is not None:
+                self.reduce(sl[1], g_s2)
+            self.reduce(sl[2], gv[pfx + "gn.scale"]); self.reduce(sl[3], gv[pfx + "gn.bias"])
             self.reduce(sl_wo, g_wo)
+            return
+        assert rows is None, "class tables are read in place by the fused segment kernels only"
+        L, st = self.L, self._st()
+        grid = L.call("magpo_row_grid", R)
+        sa, sb, du = b.get("s_a", (grid, E)), b.get("s_b", (grid, E)), b.get("g_du", (R, E))
+        ld = lambda d: 0 if d is None else E
+        L.call("magpo_resnorm_bwd", a, E, b.t["t_y" + key], E, s1, s2, d0, E, d1, ld(d1), d2, ld(d2), dsum, E, sa, sb if s2 is not None else None,
+               R, E, st)
+        self.reduce(sa, g_s1)
+        if s2 is not None:
+            self.reduce(sb, g_s2)
+        self.wgrad(b.t["t_u" + key], E, dsum, E, R, E, E, g_wo)
+        self.lin(dsum, E, wo_nat, None, du, E, R, E, E)
+        L.call("magpo_retpost_bwd", r, E, gp, ldg, gamma, beta, du, E, dr, E, dgp, lddg, sa, sb, R, self.hs, self.gs, E, st)
+        for h in range(self.nh):   # scale / bias [hs] are shared by the heads: fold the per-column slabs
+            self.reduce(sa[:, h * self.hs:], gv[pfx + "gn.scale"], P=self.hs, stride=E, accumulate=h > 0)
+            self.reduce(sb[:, h * self.hs:], gv[pfx + "gn.bias"], P=self.hs, stride=E, accumulate=h > 0)
+
+    def _class_bwd(self, side, dqkvg, dsum, kin_c, wname):
+        """Block 0 of ``side`` ("enc" / "dec") on its class table: the per-class sums of both gradient paths into the block input, then on
+        the C class rows the weight gradient of the q|k|v|g projection ``wname`` (input rows ``kin_c``) and its dX.
+        Returns (d(input) residual path [C, E], d(input) projection path [C, E], C)."""
+        L, st, b, E, cl = self.L, self._st(), self.b, self.E, self._saved["classes"]
+        _, order, offsets = cl[side]
+        i = 0 if side == "enc" else 1
+        C = cl["rows"][2 * i].shape[0]
+        dq_c, ds_c, dkin_c = b.get(f"gc_dqkvg{i}", (C, 4 * E)), b.get(f"gc_dsum{i}", (C, E)), b.get(f"gc_dkin{i}", (C, E))
+        part = b.get("gc_part_" + side[0], (L.call("magpo_class_sum_slots", C), C, 4 * E))
+        L.call("magpo_class_sum", dqkvg, 4 * E, order, offsets, C, 4 * E, part, dq_c, st)
+        L.call("magpo_class_sum", dsum, E, order, offsets, C, E, part, ds_c, st)
+        self.wgrad(kin_c, E, dq_c, 4 * E, C, E, 4 * E, self.gv[wname])
+        self.lin_dx_qkvg(dq_c, wname, dkin_c, C)
+        return ds_c, dkin_c, C
 
     # ------------------------------------------------------------------ training forward (chunkwise form)
     def train_fwd(self, obs, prev_idx, pos, dones, s0, seq_env, nseq: int, T: int, classes=None):
@@ -605,40 +569,21 @@ class SableGuider:
                 xn, qkvg = xn_c, qkvg_c
             else:
                 xn, qkvg = g(f"xn{k}"), g(f"qkvg{k}", 4 * E)
-            # (fused segments: u and y = u W_o are recomputed by the backward, which also forms the W_o gradient from them; never stored)
-            r, u = g(f"r{k}"), None if self.fused_segments else g(f"u{k}")
-            y = None if self.fused_segments else g(f"y{k}")
+            r = g(f"r{k}")
             if k > 0 or classes is None:
                 self.lin(g(f"kin{k}"), E, self.wt[f"qkvg{k}"], None, qkvg, 4 * E, R, E, 4 * E)
             self._ret_fwd(qkvg, 4 * E, qkvg[:, E:], 4 * E, qkvg[:, 2 * E:], 4 * E, r, s0[0][k], seq_env, dones, f"st_e{k}", nseq, T, 0, rows=rows)
-            if self.fused_segments and k == nb - 1:
-                # GroupNorm + gate, W_o, residual + norms, value head and the cross-retention queries of every decoder block: one launch
-                self._seg_post(1, r, qkvg[:, 3 * E:], 4 * E, v[e + "retn.gn.scale"], v[e + "retn.gn.bias"], self.wt[f"wo{k}"], xn,
-                               v[e + "ln1.scale"], v[e + "ln2.scale"], pos, u, y, rep, reppe, R, w0_t=self.wt["vh0"], b0=v["enc.head.dense0.bias"],
-                               out0=hv, ld0=E, hs=v["enc.head.norm.scale"], hw=v["enc.head.dense1.kernel"], hb1=v["enc.head.dense1.bias"],
-                               value=value, q2_t=[self.wt[f"q2{j}"] for j in range(nb)], q2=[g(f"q2{j}") for j in range(nb)], rows=rows)
-                continue
-            if self.fused_segments:
-                repb = g(f"repb{k}")
-                self._seg_post(0, r, qkvg[:, 3 * E:], 4 * E, v[e + "retn.gn.scale"], v[e + "retn.gn.bias"], self.wt[f"wo{k}"], xn,
-                               v[e + "ln1.scale"], v[e + "ln2.scale"], pos, u, y, repb, None, R, rows=rows)
-                L.call("magpo_resnorm_fwd", repb, E, None, 0, v["enc.ln.scale"], None, self.pe, pos, 1, self.npos,
-                       g(f"xn{k + 1}"), E, g(f"kin{k + 1}"), E, R, E, st)
-                continue
-            self._retpost_fwd(r, qkvg[:, 3 * E:], 4 * E, v[e + "retn.gn.scale"], v[e + "retn.gn.bias"], u, R)
-            self.lin(u, E, self.wt[f"wo{k}"], None, y, E, R, E, E)
-            if k == nb - 1:
-                L.call("magpo_resnorm_fwd", xn, E, y, E, v[e + "ln1.scale"], v[e + "ln2.scale"], self.pe, pos, 1, self.npos,
-                       rep, E, reppe, E, R, E, st)
+            if k == nb - 1:   # GroupNorm + gate, W_o, residual + norms, then the value head and the cross-retention queries of every decoder block
+                self._seg_fwd(1, f"{k}", e + "retn.", r, qkvg[:, 3 * E:], 4 * E, xn, v[e + "ln1.scale"], v[e + "ln2.scale"], pos, rep, reppe, R,
+                              w0_t=self.wt["vh0"], b0=v["enc.head.dense0.bias"], out0=hv, ld0=E, hs=v["enc.head.norm.scale"],
+                              hw=v["enc.head.dense1.kernel"], hb1=v["enc.head.dense1.bias"], value=value,
+                              q2_t=[self.wt[f"q2{j}"] for j in range(nb)], q2=[g(f"q2{j}") for j in range(nb)], rows=rows)
             else:
                 repb = g(f"repb{k}")
-                L.call("magpo_resnorm_fwd", xn, E, y, E, v[e + "ln1.scale"], v[e + "ln2.scale"], None, None, 0, 0, repb, E, None, 0, R, E, st)
+                self._seg_fwd(0, f"{k}", e + "retn.", r, qkvg[:, 3 * E:], 4 * E, xn, v[e + "ln1.scale"], v[e + "ln2.scale"], pos, repb, None, R,
+                              rows=rows)
                 L.call("magpo_resnorm_fwd", repb, E, None, 0, v["enc.ln.scale"], None, self.pe, pos, 1, self.npos,
                        g(f"xn{k + 1}"), E, g(f"kin{k + 1}"), E, R, E, st)
-        if not self.fused_segments:
-            self.lin(rep, E, self.wt["vh0"], v["enc.head.dense0.bias"], hv, E, R, E, E)
-            L.call("magpo_headmid_fwd", hv, E, v["enc.head.norm.scale"], None, 0, v["enc.head.dense1.kernel"], v["enc.head.dense1.bias"],
-                   value, 1, R, E, st)
         # ---- decoder
         if classes is not None:   # action embedding + first projection on the Cd distinct (previous action, step) rows
             prev_c, posd_c = classes["rows"][2], classes["rows"][3]
@@ -661,43 +606,20 @@ class SableGuider:
             else:
                 x, qkvg1 = g(f"x{k}"), g(f"qkvg1{k}", 4 * E)
             r1, cpe, q2, kvg2, r2 = g(f"r1{k}"), g(f"cpe{k}"), g(f"q2{k}"), g(f"kvg2{k}", 3 * E), g(f"r2{k}")
-            u1, u2, y1, y2 = (None,) * 4 if self.fused_segments else (g(f"u1{k}"), g(f"u2{k}"), g(f"y1{k}"), g(f"y2{k}"))
             if k > 0 or classes is None:
                 self.lin(g(f"xpe{k}"), E, self.wt[f"qkvg1{k}"], None, qkvg1, 4 * E, R, E, 4 * E)
             self._ret_fwd(qkvg1, 4 * E, qkvg1[:, E:], 4 * E, qkvg1[:, 2 * E:], 4 * E, r1, s0[1][k], seq_env, dones, f"st_1{k}", nseq, T, 1, rows=rows)
-            if self.fused_segments:
-                # after the self-retention: gate, W_o, residual + norm (+ pe) and the k | v | g projection of the cross-retention
-                self._seg_post(2, r1, qkvg1[:, 3 * E:], 4 * E, v[d + "retn1.gn.scale"], v[d + "retn1.gn.bias"], self.wt[f"wo1{k}"], x,
-                               v[d + "ln1.scale"], None, pos, u1, y1, None, cpe, R, w0_t=self.wt[f"kvg2{k}"], out0=kvg2, ld0=3 * E, rows=rows)
-                self._ret_fwd(q2, E, kvg2, 3 * E, kvg2[:, E:], 3 * E, r2, s0[2][k], seq_env, dones, f"st_2{k}", nseq, T, 1)
-                if k == nb - 1:   # ... and after the cross-retention of the last block the logit head
-                    self._seg_post(3, r2, kvg2[:, 2 * E:], 3 * E, v[d + "retn2.gn.scale"], v[d + "retn2.gn.bias"], self.wt[f"wo2{k}"], rep,
-                                   v[d + "ln2.scale"], v[d + "ln3.scale"], pos, u2, y2, g(f"x{nb}"), None, R, w0_t=self.wt["h0"],
-                                   b0=v["dec.head.dense0.bias"], out0=g("hp"), ld0=E, hs=v["dec.head.norm.scale"], hn=g("hn"),
-                                   w1_t=self.wt["h1"], b1=v["dec.head.dense1.bias"], logits=logits)
-                else:
-                    self._seg_post(0, r2, kvg2[:, 2 * E:], 3 * E, v[d + "retn2.gn.scale"], v[d + "retn2.gn.bias"], self.wt[f"wo2{k}"], rep,
-                                   v[d + "ln2.scale"], v[d + "ln3.scale"], pos, u2, y2, g(f"x{k + 1}"), g(f"xpe{k + 1}"), R)
-                continue
-            self._retpost_fwd(r1, qkvg1[:, 3 * E:], 4 * E, v[d + "retn1.gn.scale"], v[d + "retn1.gn.bias"], u1, R)
-            self.lin(u1, E, self.wt[f"wo1{k}"], None, y1, E, R, E, E)
-            L.call("magpo_resnorm_fwd", x, E, y1, E, v[d + "ln1.scale"], None, self.pe, pos, 1, self.npos, None, 0, cpe, E, R, E, st)   # only c + pe is consumed
-            self.lin(reppe, E, self.wt[f"q2{k}"], None, q2, E, R, E, E)
-            self.lin(cpe, E, self.wt[f"kvg2{k}"], None, kvg2, 3 * E, R, E, 3 * E)
+            # after the self-retention: gate, W_o, residual + norm + pe (only c + pe is consumed) and the k | v | g projection of the cross-retention
+            self._seg_fwd(2, f"1{k}", d + "retn1.", r1, qkvg1[:, 3 * E:], 4 * E, x, v[d + "ln1.scale"], None, pos, None, cpe, R,
+                          w0_t=self.wt[f"kvg2{k}"], out0=kvg2, ld0=3 * E, rows=rows)
             self._ret_fwd(q2, E, kvg2, 3 * E, kvg2[:, E:], 3 * E, r2, s0[2][k], seq_env, dones, f"st_2{k}", nseq, T, 1)
-            self._retpost_fwd(r2, kvg2[:, 2 * E:], 3 * E, v[d + "retn2.gn.scale"], v[d + "retn2.gn.bias"], u2, R)
-            self.lin(u2, E, self.wt[f"wo2{k}"], None, y2, E, R, E, E)
-            if k == nb - 1:
-                L.call("magpo_resnorm_fwd", rep, E, y2, E, v[d + "ln2.scale"], v[d + "ln3.scale"], None, None, 0, 0, g(f"x{nb}"), E,
-                       None, 0, R, E, st)
+            if k == nb - 1:   # ... and after the cross-retention of the last block the logit head
+                self._seg_fwd(3, f"2{k}", d + "retn2.", r2, kvg2[:, 2 * E:], 3 * E, rep, v[d + "ln2.scale"], v[d + "ln3.scale"], pos, g(f"x{nb}"), None, R,
+                              w0_t=self.wt["h0"], b0=v["dec.head.dense0.bias"], out0=g("hp"), ld0=E, hs=v["dec.head.norm.scale"], hn=g("hn"),
+                              w1_t=self.wt["h1"], b1=v["dec.head.dense1.bias"], logits=logits)
             else:
-                L.call("magpo_resnorm_fwd", rep, E, y2, E, v[d + "ln2.scale"], v[d + "ln3.scale"], self.pe, pos, 1, self.npos,
-                       g(f"x{k + 1}"), E, g(f"xpe{k + 1}"), E, R, E, st)
-        if not self.fused_segments:
-            hp, hn = g("hp"), g("hn")
-            self.lin(g(f"x{nb}"), E, self.wt["h0"], v["dec.head.dense0.bias"], hp, E, R, E, E)
-            L.call("magpo_headmid_fwd", hp, E, v["dec.head.norm.scale"], hn, E, None, None, None, 0, R, E, st)
-            self.lin(hn, E, self.wt["h1"], v["dec.head.dense1.bias"], logits, LW, R, E, K)
+                self._seg_fwd(0, f"2{k}", d + "retn2.", r2, kvg2[:, 2 * E:], 3 * E, rep, v[d + "ln2.scale"], v[d + "ln3.scale"], pos,
+                              g(f"x{k + 1}"), g(f"xpe{k + 1}"), R)
         return logits, value
 
     # ------------------------------------------------------------------ training backward
@@ -731,18 +653,8 @@ class SableGuider:
             dsum2 = g(f"dsum2_{k}")
             dr2 = g("dr"); dq2 = g(f"dq2_{k}"); dkvg2 = g(f"dkvg2_{k}", 3 * E)
             kvg2 = t(f"kvg2{k}")
-            if self.fused_segments:
-                self._seg_bwd(t("rep"), None, v[d + "ln2.scale"], v[d + "ln3.scale"], din0, din1, None, v[d + "retn2.w_o"], t(f"r2{k}"),
-                              kvg2[:, 2 * E:], 3 * E, d + "retn2.", dsum2, dr2, dkvg2[:, 2 * E:], 3 * E, R, gv[d + "ln2.scale"], gv[d + "ln3.scale"],
-                              wo_t=self.wt[f"wo2{k}"], g_wo=gv[d + "retn2.w_o"])
-            else:
-                L.call("magpo_resnorm_bwd", t("rep"), E, t(f"y2{k}"), E, v[d + "ln2.scale"], v[d + "ln3.scale"], din0, E, din1, E if din1 is not None else 0,
-                       None, 0, dsum2, E, slab("a"), slab("b"), R, E, st)
-                self.reduce(slab("a"), gv[d + "ln2.scale"]); self.reduce(slab("b"), gv[d + "ln3.scale"])
-                self.wgrad(t(f"u2{k}"), E, dsum2, E, R, E, E, gv[d + "retn2.w_o"])
-                du2 = g("du")
-                self.lin(dsum2, E, v[d + "retn2.w_o"], None, du2, E, R, E, E)
-                self._retpost_bwd(t(f"r2{k}"), kvg2[:, 2 * E:], 3 * E, d + "retn2.", du2, dr2, dkvg2[:, 2 * E:], 3 * E, R, slab("a"), slab("b"))
+            self._seg_bwd(f"2{k}", d + "retn2.", t("rep"), v[d + "ln2.scale"], v[d + "ln3.scale"], din0, din1, None, t(f"r2{k}"),
+                          kvg2[:, 2 * E:], 3 * E, dsum2, dr2, dkvg2[:, 2 * E:], 3 * E, R, gv[d + "ln2.scale"], gv[d + "ln3.scale"])
             self._ret_bwd(t(f"q2{k}"), E, kvg2, 3 * E, kvg2[:, E:], 3 * E, dr2, dq2, E, dkvg2, 3 * E, dkvg2[:, E:], 3 * E, dones,
                           f"st_2{k}", nseq, T, 1)
             self.wgrad(t("reppe"), E, dq2, E, R, E, E, gv[d + "retn2.w_q"])
@@ -759,31 +671,13 @@ class SableGuider:
             dr1 = g("dr"); dqkvg1 = g(f"dqkvg1_{k}", 4 * E)
             rows = cl["dec"][0] if sv["direct"] and k == 0 else None
             qkvg1, xk = (b.t["c_qkvg10"], b.t["c_x0"]) if rows is not None else (t(f"qkvg1{k}"), t(f"x{k}"))
-            if self.fused_segments:
-                self._seg_bwd(xk, None, v[d + "ln1.scale"], None, dcpe, None, None, v[d + "retn1.w_o"], t(f"r1{k}"),
-                              qkvg1[:, 3 * E:], 4 * E, d + "retn1.", dsum1, dr1, dqkvg1[:, 3 * E:], 4 * E, R, gv[d + "ln1.scale"], None, rows=rows,
-                              wo_t=self.wt[f"wo1{k}"], g_wo=gv[d + "retn1.w_o"])
-            else:
-                L.call("magpo_resnorm_bwd", t(f"x{k}"), E, t(f"y1{k}"), E, v[d + "ln1.scale"], None, dcpe, E, None, 0, None, 0, dsum1, E,
-                       slab("a"), None, R, E, st)
-                self.reduce(slab("a"), gv[d + "ln1.scale"])
-                self.wgrad(t(f"u1{k}"), E, dsum1, E, R, E, E, gv[d + "retn1.w_o"])
-                du1 = g("du")
-                self.lin(dsum1, E, v[d + "retn1.w_o"], None, du1, E, R, E, E)
-                self._retpost_bwd(t(f"r1{k}"), qkvg1[:, 3 * E:], 4 * E, d + "retn1.", du1, dr1, dqkvg1[:, 3 * E:], 4 * E, R, slab("a"), slab("b"))
+            self._seg_bwd(f"1{k}", d + "retn1.", xk, v[d + "ln1.scale"], None, dcpe, None, None, t(f"r1{k}"), qkvg1[:, 3 * E:], 4 * E,
+                          dsum1, dr1, dqkvg1[:, 3 * E:], 4 * E, R, gv[d + "ln1.scale"], None, rows=rows)
             self._ret_bwd(qkvg1, 4 * E, qkvg1[:, E:], 4 * E, qkvg1[:, 2 * E:], 4 * E, dr1, dqkvg1, 4 * E, dqkvg1[:, E:], 4 * E,
                           dqkvg1[:, 2 * E:], 4 * E, dones, f"st_1{k}", nseq, T, 1, rows=rows)
             if k == 0 and cl is not None:   # block 0 on the class table: per-class sums of both gradient paths, then Cd rows
-                _, order, offsets = cl["dec"]
-                Cd = cl["rows"][2].shape[0]
-                dq_c, ds_c = b.get("gc_dqkvg1", (Cd, 4 * E)), b.get("gc_dsum1", (Cd, E))
-                part = b.get("gc_part_d", (L.call("magpo_class_sum_slots", Cd), Cd, 4 * E))
-                L.call("magpo_class_sum", dqkvg1, 4 * E, order, offsets, Cd, 4 * E, part, dq_c, st)
-                L.call("magpo_class_sum", dsum1, E, order, offsets, Cd, E, part, ds_c, st)
-                self.wgrad(b.t["c_xpe0"], E, dq_c, 4 * E, Cd, E, 4 * E, gv[d + "retn1.w_qkvg"])
-                dkin1 = b.get("gc_dkin1", (Cd, E))
-                self.lin_dx_qkvg(dq_c, d + "retn1.w_qkvg", dkin1, Cd)
-                din0, din1, prev_idx, Rd = ds_c, dkin1, cl["rows"][2], Cd
+                din0, din1, Rd = self._class_bwd("dec", dqkvg1, dsum1, b.t["c_xpe0"], d + "retn1.w_qkvg")
+                prev_idx = cl["rows"][2]
                 break
             self.wgrad(t(f"xpe{k}"), E, dqkvg1, 4 * E, R, E, 4 * E, gv[d + "retn1.w_qkvg"])
             dkin1 = g(f"dkin1_{k}")
@@ -813,31 +707,13 @@ class SableGuider:
             dr = g("dr"); dqkvg = g(f"dqkvg_{k}", 4 * E)
             rows = cl["enc"][0] if sv["direct"] and k == 0 else None
             qkvg, xnk = (b.t["c_qkvg0"], b.t["c_xn0"]) if rows is not None else (t(f"qkvg{k}"), t(f"xn{k}"))
-            if self.fused_segments:
-                self._seg_bwd(xnk, None, v[e + "ln1.scale"], v[e + "ln2.scale"], e0, e1, e2, v[e + "retn.w_o"], t(f"r{k}"),
-                              qkvg[:, 3 * E:], 4 * E, e + "retn.", dsum0, dr, dqkvg[:, 3 * E:], 4 * E, R, gv[e + "ln1.scale"], gv[e + "ln2.scale"], rows=rows,
-                              wo_t=self.wt[f"wo{k}"], g_wo=gv[e + "retn.w_o"])
-            else:
-                L.call("magpo_resnorm_bwd", t(f"xn{k}"), E, t(f"y{k}"), E, v[e + "ln1.scale"], v[e + "ln2.scale"], e0, E, e1, E if e1 is not None else 0,
-                       e2, E if e2 is not None else 0, dsum0, E, slab("a"), slab("b"), R, E, st)
-                self.reduce(slab("a"), gv[e + "ln1.scale"]); self.reduce(slab("b"), gv[e + "ln2.scale"])
-                self.wgrad(t(f"u{k}"), E, dsum0, E, R, E, E, gv[e + "retn.w_o"])
-                du = g("du")
-                self.lin(dsum0, E, v[e + "retn.w_o"], None, du, E, R, E, E)
-                self._retpost_bwd(t(f"r{k}"), qkvg[:, 3 * E:], 4 * E, e + "retn.", du, dr, dqkvg[:, 3 * E:], 4 * E, R, slab("a"), slab("b"))
+            self._seg_bwd(f"{k}", e + "retn.", xnk, v[e + "ln1.scale"], v[e + "ln2.scale"], e0, e1, e2, t(f"r{k}"), qkvg[:, 3 * E:], 4 * E,
+                          dsum0, dr, dqkvg[:, 3 * E:], 4 * E, R, gv[e + "ln1.scale"], gv[e + "ln2.scale"], rows=rows)
             self._ret_bwd(qkvg, 4 * E, qkvg[:, E:], 4 * E, qkvg[:, 2 * E:], 4 * E, dr, dqkvg, 4 * E, dqkvg[:, E:], 4 * E, dqkvg[:, 2 * E:], 4 * E,
                           dones, f"st_e{k}", nseq, T, 0, rows=rows)
             if k == 0 and cl is not None:
-                _, order, offsets = cl["enc"]
+                ds_c, dkin, Ce = self._class_bwd("enc", dqkvg, dsum0, b.t["c_kin0"], e + "retn.w_qkvg")
                 obs_c = cl["rows"][0]
-                Ce = obs_c.shape[0]
-                dq_c, ds_c = b.get("gc_dqkvg0", (Ce, 4 * E)), b.get("gc_dsum0", (Ce, E))
-                part = b.get("gc_part_e", (L.call("magpo_class_sum_slots", Ce), Ce, 4 * E))
-                L.call("magpo_class_sum", dqkvg, 4 * E, order, offsets, Ce, 4 * E, part, dq_c, st)
-                L.call("magpo_class_sum", dsum0, E, order, offsets, Ce, E, part, ds_c, st)
-                self.wgrad(b.t["c_kin0"], E, dq_c, 4 * E, Ce, E, 4 * E, gv[e + "retn.w_qkvg"])
-                dkin = b.get("gc_dkin0", (Ce, E))
-                self.lin_dx_qkvg(dq_c, e + "retn.w_qkvg", dkin, Ce)
                 gride = L.call("magpo_row_grid", Ce)
                 sa, sw, sd = b.get("s_a_e", (gride, E)), b.get("s_w_e", (gride, 32 * E)), b.get("s_d_e", (gride, 32))
                 L.call("magpo_embed_bwd", 0, None, 0, ds_c, E, dkin, E, None, 0, v["enc.ln.scale"], None, 0, sa, sw, F,
@@ -873,8 +749,7 @@ class SableGuider:
                 self.reduce(slab("a"), gv["enc.ln.scale"], accumulate=not first_ln)
                 self.reduce(slab("d", 32), gv["enc.obs.norm.scale"], P=F, stride=32)
                 self.reduce(slab("w", 32 * E), gv["enc.obs.dense.kernel"], P=F * E, stride=32 * E)
-        if self.overlap_wgrad and self.wgrad_stream is not None:
-            torch.cuda.current_stream().wait_stream(self.wgrad_stream)
+        self._join_wgrad()
         if self.emb is not None:   # gradient of a logical parameter = sum over its tied device copies
             self.emb.fold(self.grads_D, self.grads)
 

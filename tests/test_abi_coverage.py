@@ -23,7 +23,7 @@ INDIRECT = {
     "magpo_mpe_reset": "tests.test_mpe_gpu::test_mpe_env_matches_restatement",                      # MpeEnvBatch
     "magpo_mpe_step": "tests.test_mpe_gpu::test_mpe_env_matches_restatement",
     "magpo_sable_act": "tests.test_act_instances_gpu::test_forced_instance_equals_kernel_composition_under_graph_replay",   # SableGuider.act_fused
-    "magpo_act_weight_layout": "tests.test_act_instances_gpu::test_forced_instance_equals_kernel_composition_under_graph_replay",   # build_act_weights
+    "magpo_act_weight_layout": "tests.test_act_instances_gpu::test_forced_instance_equals_kernel_composition_under_graph_replay",   # SableGuider.refresh
 }
 
 

@@ -222,3 +222,39 @@ def test_size_dispatched_instance_equals_composition_at_bench_sizes(N, A, K, nb,
     close(b["last_val"].reshape(N, A)[ok], a["last_val"].reshape(N, A)[ok], 3e-5, 1e-6, "last_val")
     for x, y in zip(a["hs"], b["hs"]):
         close(y[:, :, ok], x[:, :, ok], 3e-5, 1e-6, "sable state")
+
+
+@pytest.mark.parametrize("nb", [1, 2])
+def test_act_fused_follows_a_parameter_update(nb):
+    """The fused acting kernel reads its own (fragment-major) copies of the weights.  After the parameters change and ``refresh()`` ran,
+    a stand-alone ``act_fused`` must act on the NEW parameters: equal to ``act()`` (the kernel composition, which reads the transposed
+    copies) on the same parameters and the same non-zero carried states -- actions bit-equal, values / log-probs / states at the
+    tolerances of test_fused_act_equals_kernel_composition (tests/test_learner_gpu.py).  Stale copies would be off by the 1 % the
+    parameters moved."""
+    from magpo_amd.sable import SableGuider
+    A, K, N = 3, 10, 6
+    g = SableGuider(A, K, A + 1, DEV, n_block=nb, seed=9, wgrad_groups=4)
+    gen = torch.Generator().manual_seed(3)
+    obs = torch.randn(N, A, A + 1, generator=gen).to(DEV)
+    pos = torch.tensor([3, 4, 5, 6, 7, 8], dtype=torch.int32, device=DEV)   # mid-episode; no ``done``: the carried states are read
+    keys = np.array([[11, 12], [13, 14], [15, 16]], dtype=np.uint32)
+
+    def outs():
+        return torch.zeros(N, A, dtype=torch.int32, device=DEV), torch.zeros(N, A, device=DEV), torch.zeros(N, A, device=DEV)
+
+    states = tuple(torch.zeros(nb, g.ntile, N, 64, 64, device=DEV) for _ in range(3))
+    g.act_fused(obs, pos, states, keys, *outs())          # builds the pointer tables, leaves non-zero states
+    assert all(float(s.abs().max()) > 0 for s in states)
+    with torch.no_grad():
+        g.P.flat.mul_(1.01)
+    g.refresh()
+    sf, sc = tuple(s.clone() for s in states), tuple(s.clone() for s in states)
+    (af, lf, vf), (ac, lc, vc) = outs(), outs()
+    g.act_fused(obs, pos + 1, sf, keys, af, lf, vf)
+    g.act(obs, pos + 1, sc, keys, ac, lc, vc)
+    torch.cuda.synchronize()
+    assert torch.equal(af, ac), "actions after the parameter update differ from the kernel composition"
+    close(vf, vc, 1e-5, 1e-6, "value")
+    close(lf, lc, 1e-5, 1e-6, "log_prob")
+    for x, y in zip(sf, sc):
+        close(x, y, 1e-5, 1e-6, "sable state")

@@ -161,25 +161,32 @@ def test_rollout_and_update_parity(A, K, TL, maxval, N, T, nb, nh, E):
     assert dl.groups[0].graph is not None, "the rollouts of steps 2 and 3 should have been a HIP-graph capture / replay"
 
 
-def test_graph_replay_equals_eager_rollout():
-    """The HIP-graph replay of the rollout must reproduce the eager rollout bit for bit (same kernels, same order)."""
+@pytest.mark.parametrize("num_groups", [1, 2])
+def test_graph_replay_equals_eager_rollout(num_groups):
+    """The HIP-graph replay of the rollout must reproduce the eager rollout bit for bit (same kernels, same order).  Two groups: from the
+    third step on their graphs replay side by side on separate streams, all reading the guider's one set of weight copies."""
     from magpo_amd.learner import CoordSumConfig, MagpoLearner, SystemConfig, host_split, prng_key
     sysc = SystemConfig(rollout_length=9, ppo_epochs=1, num_minibatches=1)   # odd T: exercises the buffer-role fix-up
     key = host_split(prng_key(5), 4)[0]
     ls = []
     for use_graph in (False, True):
-        l = MagpoLearner(CoordSumConfig(3, 10, 7, 30), 8, sysc, "cuda", net_seed=4, wgrad_groups=4)
+        l = MagpoLearner(CoordSumConfig(3, 10, 7, 30), 8, sysc, "cuda", net_seed=4, wgrad_groups=4, num_groups=num_groups)
         l.use_graph = use_graph
-        l.setup(key)
+        l.setup(key, n_groups=num_groups)
         ls.append(l)
+    eager, graphed = ls
+    # the side-by-side replay branch of rollout() needs the class tables (and the fused acting kernel with the batched actor carry)
+    assert graphed.class_tables and graphed.fused_act and graphed.batched_actor_carry and len(graphed.groups) == num_groups
     for it in range(4):
         for l in ls:
             l.update_step()
-        assert ls[1].groups[0].graph is not None or it < 1, "rollout should be captured from the second call on"
-        for k in ("action", "value", "log_prob", "reward", "adv"):
-            assert torch.equal(ls[0].traj[k], ls[1].traj[k]), (it, k)
-        assert torch.equal(ls[0].guider.P.flat, ls[1].guider.P.flat) and np.array_equal(ls[0].key, ls[1].key)
-    assert not ls[1].groups[0].graph_failed
+        assert all(g.graph is not None for g in graphed.groups) or it < 1, "every group's rollout should be captured from the second call on"
+        for gi, (ge, gg) in enumerate(zip(eager.groups, graphed.groups)):
+            for k in ("action", "value", "log_prob", "reward", "adv"):
+                assert torch.equal(ge.traj[k], gg.traj[k]), (it, gi, k)
+            assert np.array_equal(ge.key, gg.key)
+        assert torch.equal(eager.guider.P.flat, graphed.guider.P.flat), it
+    assert not any(g.graph_failed for g in graphed.groups) and all(g.graph is None for g in eager.groups)
 
 
 @pytest.mark.parametrize("A,K,N,nb,nh", [(4, 20, 70, 1, 1), (5, 15, 33, 2, 2), (16, 6, 40, 1, 4)])
