@@ -317,6 +317,7 @@ int magpo_sample_categorical(const float* logits, long ld, const unsigned char* 
 int magpo_gae(const float* reward, const float* value, const unsigned char* done, const float* last_val,
               const unsigned char* last_done, float* adv, float* targets, int T, int N, int A, float gamma,
               float lam, magpo_stream_t stream);
+/* o_h0idx [mb][A] (nullable): row env * A + agent of every gathered sequence's start state, which only the GRU actor reads. */
 int magpo_gather_minibatch(const float* obs, const int* action, const int* stepcount, const unsigned char* done,
                            const unsigned char* mask, const float* value, const float* logp, const float* adv,
                            const float* targets, const int* env_idx, const int* agent_perm, float* o_obs,
@@ -340,6 +341,16 @@ int magpo_loss_fwd_bwd(const float* g_logits, long ldg, const float* a_logits, l
                        long lddg, float* da_logits, long lddda, float* dvalue, double* workspace, float* loss_out,
                        long R, int K, float clip_eps, float clip_gpo, float ent_coef, float vf_coef, float alpha,
                        magpo_stream_t stream);
+/* PPO loss of the guider-only system (rec_sable.py:177-226): the guider half of magpo_loss_fwd_bwd without an actor.  Same contracts as
+ * dg_logits there: columns K .. min(lddl, 64) and illegal columns exactly 0, a row with one legal action has no gradient, input columns
+ * >= K are loaded and discarded, two-stage reduction in a fixed order (bit-stable), workspace >= 8 * 1024 doubles.
+ * loss_out [4] = [total, actor_loss, entropy, value_loss], total = actor - ent_coef entropy + vf_coef value; dlogits / dvalue = d total.
+ * Rejected before any launch: R < 1, K > 64, K > ld, K > lddl, lddl not a multiple of 4. */
+int magpo_ppo_loss_fwd_bwd(const float* logits, long ld, const unsigned char* mask, const int* action,
+                           const float* old_logp, const float* old_value, const float* value, const float* adv,
+                           const float* targets, const float* adv_stats, float* dlogits, long lddl, float* dvalue,
+                           double* workspace, float* loss_out, long R, int K, float clip_eps, float ent_coef,
+                           float vf_coef, magpo_stream_t stream);
 int magpo_copy_rows(const float* src, long lds_, float* dst, long ldd, long R, int W, magpo_stream_t stream);
 
 /* ---- K10 optimiser: optax clip_by_global_norm + adam(eps=1e-5) (rec_magpo.py:581-589, :412-420) ---- */

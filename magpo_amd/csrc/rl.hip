@@ -157,7 +157,7 @@ __global__ void k_gather_minibatch(GatherArgs g) {
   g.o_targets[r] = g.targets[src];
   if (g.mask) for (int k = 0; k < g.K; ++k) g.o_mask[r * g.K + k] = g.mask[src * g.K + k];
   if (ap == 0) g.o_done[(long)j * g.T + t] = g.done[(long)t * g.N + env];
-  if (t == 0) g.o_h0idx[(long)j * g.A + ap] = env * g.A + ag;
+  if (t == 0 && g.o_h0idx) g.o_h0idx[(long)j * g.A + ap] = env * g.A + ag;   // (nullable: only the GRU actor reads it)
 }
 
 // ---- moments of the advantages (rec_magpo.py:283,356): mean and 1/(std + 1e-8), population std ------
@@ -361,6 +361,120 @@ __global__ void k_loss_final(const double* __restrict__ part, int nb, float inv_
   out[0] = tg + ta; out[1] = vl; out[2] = apl; out[3] = pg; out[4] = klm; out[5] = ent; out[6] = kl; out[7] = tg; out[8] = ta;
 }
 
+// ---- PPO loss of the guider-only system (rec_sable.py:177-226) + gradients w.r.t. logits / value ------------------
+// The guider half of k_magpo_loss without the actor: with a_logits = g_logits the MAGPO guider surrogate has d = 0, no KL mask and
+// clipped_ratio = ratio, which is this loss.  Same row layout (16 lanes per row, 4 columns per lane), same masking, same entropy.
+// The row code duplicates k_magpo_loss's so that k_magpo_loss's code generation does not change; tests/test_sable_loss_gpu.py keeps the two
+// in step (the MAGPO kernel at a_logits = g_logits must give this kernel's gradients and scalars; rows on each kink must take one of the
+// enumerated one-sided values).
+struct PpoLossArgs {
+  const float* logits; long ld; const unsigned char* mask; const int* action; const float* old_logp; const float* old_value;
+  const float* value; const float* adv; const float* targets; const float* adv_stats;   // [mean, 1/(std+1e-8)]
+  float* dlogits; long lddl; float* dvalue;
+  double* part;   // [grid][8] partial sums: actor_loss, entropy, value_loss, 0 ...
+  long R; int K;
+  float clip_eps, ent_coef, vf_coef, inv_R;
+};
+__global__ __launch_bounds__(256) void k_ppo_loss(PpoLossArgs a) {
+  __shared__ double sh[3][4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l16 = lane & 15, c4 = 4 * l16;
+  float acc[3] = {0.f, 0.f, 0.f};
+  const long nrow4 = (a.R + 3) / 4;
+  const bool vec = a.ld >= 64 && (a.ld & 3) == 0;   // whole padded rows: one unconditional float4 per lane
+  for (long base = (long)blockIdx.x * 4 + wave; base < nrow4; base += (long)gridDim.x * 4) {
+    const long r = base * 4 + (lane >> 4);
+    const bool ok = r < a.R;
+    const long rr = ok ? r : 0;
+    float lv[4], x[4];
+    bool legal[4];
+    if (vec) {
+      const float4 v = *reinterpret_cast<const float4*>(a.logits + rr * a.ld + c4);
+      lv[0] = v.x; lv[1] = v.y; lv[2] = v.z; lv[3] = v.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) lv[j] = c4 + j < a.K ? a.logits[rr * a.ld + c4 + j] : 0.f;
+    }
+    unsigned char mk[4] = {1, 1, 1, 1};
+    if (a.mask) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) mk[j] = a.mask[rr * a.K + (c4 + j < a.K ? c4 + j : 0)];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool in = c4 + j < a.K;
+      legal[j] = in && mk[j];
+      x[j] = in ? (legal[j] ? lv[j] : FMIN) : -INFINITY;   // columns >= K: loaded, discarded
+    }
+    const float mx = max16(fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])));
+    float se = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) se += expf(x[j] - mx);
+    const float lse = mx + logf(sum16(se));
+    const int act = a.action[rr];
+    float lp[4], p[4];
+    float ent = 0.f, logp = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      lp[j] = x[j] - lse;
+      p[j] = expf(lp[j]);
+      ent -= p[j] != 0.f ? p[j] * lp[j] : 0.f;
+      logp = c4 + j == act ? lp[j] : logp;
+    }
+    ent = sum16(ent); logp = sum16(logp);
+    const float A_ = (a.adv[rr] - a.adv_stats[0]) * a.adv_stats[1];
+    const float eps = a.clip_eps;
+    // clipped surrogate (rec_sable.py:197-210)
+    const float ratio = expf(logp - a.old_logp[rr]);
+    const float rc = fminf(fmaxf(ratio, 1.f - eps), 1.f + eps);
+    const float l1 = ratio * A_, l2 = rc * A_;
+    const float pgl = -fminf(l1, l2);
+    const float dl2 = (ratio > 1.f - eps && ratio < 1.f + eps) ? l1 : 0.f;
+    const float c_g = -(min_grad_weight(l1, l2, true) * l1 + min_grad_weight(l1, l2, false) * dl2);
+    // clipped value loss (:214-219)
+    const float v = a.value[rr], vo = a.old_value[rr], tg = a.targets[rr];
+    const float dv = v - vo;
+    const float vcl = vo + fminf(fmaxf(dv, -eps), eps);
+    const float e1 = (v - tg) * (v - tg), e2 = (vcl - tg) * (vcl - tg);
+    const float vl = 0.5f * fmaxf(e1, e2);
+    const float g1 = 2.f * (v - tg);
+    const float g2 = (dv > -eps && dv < eps) ? 2.f * (vcl - tg) : 0.f;
+    const float dvl = 0.5f * (e1 > e2 ? g1 : (e2 > e1 ? g2 : 0.5f * (g1 + g2)));
+    if (ok) {
+      float4 og;
+      float* pog = &og.x;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float onehot = (c4 + j == act) ? 1.f : 0.f;
+        float gg = c_g * (onehot - p[j]);
+        gg += (p[j] != 0.f) ? a.ent_coef * p[j] * (lp[j] + ent) : 0.f;
+        pog[j] = legal[j] ? a.inv_R * gg : 0.f;
+      }
+      if (c4 + 3 < a.lddl) *reinterpret_cast<float4*>(a.dlogits + r * a.lddl + c4) = og;   // lddl is a multiple of 4: whole float4 or nothing
+      if (l16 == 0) {
+        a.dvalue[r] = a.inv_R * a.vf_coef * dvl;
+        acc[0] += pgl; acc[1] += ent; acc[2] += vl;
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    const float w = wave_sum(acc[q]);
+    if (lane == 0) sh[q][wave] = (double)w;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) a.part[8 * blockIdx.x + threadIdx.x] = (sh[threadIdx.x][0] + sh[threadIdx.x][1]) + (sh[threadIdx.x][2] + sh[threadIdx.x][3]);
+}
+// out: [total, actor_loss, entropy, value_loss]
+__global__ void k_ppo_loss_final(const double* __restrict__ part, int nb, float inv_R, float ent_coef, float vf_coef, float* __restrict__ out) {
+  if (blockIdx.x != 0 || threadIdx.x >= 64) return;
+  double s[3];
+#pragma unroll
+  for (int q = 0; q < 3; ++q) s[q] = wave_sum_strided(part, nb, 8, q);
+  if (threadIdx.x != 0) return;
+  const float pg = (float)(s[0] * inv_R), ent = (float)(s[1] * inv_R), vl = (float)(s[2] * inv_R);
+  out[0] = pg - ent_coef * ent + vf_coef * vl; out[1] = pg; out[2] = ent; out[3] = vl;
+}
+
 // misc small kernels ----------------------------------------------------------------------------
 __global__ void k_copy_rows_f32(const float* __restrict__ src, long lds_, float* __restrict__ dst, long ldd, long R, int W) {
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -467,6 +581,25 @@ extern "C" int magpo_loss_fwd_bwd(const float* g_logits, long ldg, const float* 
   hipLaunchKernelGGL(k_magpo_loss, dim3(nb), dim3(256), 0, st, a);
   hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(64), 0, st, workspace, nb, 1.0f / (float)R, ent_coef, vf_coef, alpha, loss_out);
   return check_launch("magpo_loss_fwd_bwd");
+}
+
+// workspace: >= 8*1024 doubles (as magpo_loss_fwd_bwd); loss_out: 4 floats [total, actor_loss, entropy, value_loss]
+extern "C" int magpo_ppo_loss_fwd_bwd(const float* logits, long ld, const unsigned char* mask, const int* action,
+                                      const float* old_logp, const float* old_value, const float* value, const float* adv,
+                                      const float* targets, const float* adv_stats, float* dlogits, long lddl, float* dvalue,
+                                      double* workspace, float* loss_out, long R, int K, float clip_eps, float ent_coef,
+                                      float vf_coef, hipStream_t st) {
+  if (R <= 0 || K > 64 || K > ld || K > lddl || (lddl & 3)) {   // (R = 0: an empty grid and a mean over no rows)
+    set_error("ppo loss: need R >= 1, K <= 64, K <= strides, gradient stride a multiple of 4");
+    return MAGPO_EINVAL;
+  }
+  int nb = (int)((R + 15) / 16);
+  if (nb > 1024) nb = 1024;
+  PpoLossArgs a{logits, ld, mask, action, old_logp, old_value, value, adv, targets, adv_stats, dlogits, lddl, dvalue, workspace,
+                R, K, clip_eps, ent_coef, vf_coef, 1.0f / (float)R};
+  hipLaunchKernelGGL(k_ppo_loss, dim3(nb), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_ppo_loss_final, dim3(1), dim3(64), 0, st, workspace, nb, 1.0f / (float)R, ent_coef, vf_coef, loss_out);
+  return check_launch("magpo_ppo_loss_fwd_bwd");
 }
 
 extern "C" int magpo_copy_rows(const float* src, long lds_, float* dst, long ldd, long R, int W, hipStream_t st) {

@@ -59,7 +59,7 @@ class EnvGroup:
     reference's (device, update-batch) replica (rec_magpo.py:519, :648-653); all groups of a process share
     the parameters and the training workspaces."""
 
-    def __init__(self, env_cfg, N: int, T: int, device, n_block: int = 1, n_tile: int = 1):
+    def __init__(self, env_cfg, N: int, T: int, device, n_block: int = 1, n_tile: int = 1, policy: bool = True):
         A, F = env_cfg.num_agents, obs_row_stride(env_cfg.obs_dim)
         f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=device)
         i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
@@ -74,8 +74,9 @@ class EnvGroup:
         # the one 128-wide head (SableGuider.ntile)
         self.sable_hs = tuple(f32(n_block, n_tile, N, 64, 64) for _ in range(3))
         self.prev_sable_hs = tuple(f32(n_block, n_tile, N, 64, 64) for _ in range(3))
-        self.policy_h = [f32(N * A, 128), f32(N * A, 128)]
-        self.policy_h0 = f32(N * A, 128)
+        # GRU actor hidden states (double-buffered) and their rollout-start copy; a guider-only system has none
+        self.policy_h = [f32(N * A, 128), f32(N * A, 128)] if policy else None
+        self.policy_h0 = f32(N * A, 128) if policy else None
         self.last_val = f32(N, A)
         self.key = prng_key(0)
         self.cur = 0
@@ -86,6 +87,11 @@ class EnvGroup:
 
 
 class MagpoLearner:
+    # What a guider-only system (sable_learner.SableLearner) turns off: the GRU actor with its hidden states, carry, training pass and
+    # optimiser.  Everything else -- env groups, rollout body, HIP-graph capture, gather, shuffles, micro-batches, update loop -- is shared.
+    has_actor = True
+    n_loss = 9      # loss scalars behind the gradients in the all-reduce message (k_loss_final)
+
     def __init__(self, env_cfg, num_envs: int, sys: SystemConfig, device, *, net_seed: Optional[int] = 0,
                  decay_scaling_factor: float = 0.8, use_pe: bool = True, wgrad_groups: int = 512, num_groups: int = 1,
                  n_block: int = 1, n_head: int = 1, embed_dim: int = 64, tuning=None, guider: Optional[SableGuider] = None,
@@ -113,7 +119,7 @@ class MagpoLearner:
             n_block, n_head, embed_dim = guider.nb, guider.nh, guider.EL
         self.nb, self.nh = int(n_block), int(n_head)
         gn = FlatParams(guider_layout(int(embed_dim), F, K, self.nb, self.nh), "cpu").numel
-        an = actor.P.numel if actor is not None else FlatParams(actor_layout(F, 128, K, *actor_torso), "cpu").numel
+        an = 0 if not self.has_actor else actor.P.numel if actor is not None else FlatParams(actor_layout(F, 128, K, *actor_torso), "cpu").numel
         self.grad_all = torch.zeros(gn + an + 16, dtype=torch.float32, device=device)
         self.grad_acc = torch.zeros_like(self.grad_all) if num_groups > 1 else None
         self.grad_mu = torch.zeros_like(self.grad_all) if sys.micro_batches > 1 else None
@@ -123,32 +129,38 @@ class MagpoLearner:
                                  seed=None if net_seed is None else net_seed, grads=self.grad_all[:gn], tuning=self.tuning, obs_ld=self.Fld)
         else:
             guider.bind_grads(self.grad_all[:gn])
-        if actor is None:
+        if not self.has_actor:
+            actor = None
+        elif actor is None:
             actor = GruActor(A, K, F, device, wgrad_groups=wgrad_groups, seed=None if net_seed is None else net_seed + 1,
                              grads=self.grad_all[gn:gn + an], tuning=self.tuning, obs_ld=self.Fld, pre_torso=actor_torso[0],
                              post_torso=actor_torso[1])
         else:
             actor.bind_grads(self.grad_all[gn:gn + an])
-        if guider.F != F or actor.F != F or guider.Fld != self.Fld or actor.Fld != self.Fld:
-            raise ValueError(f"networks built for {guider.F} / {actor.F} observation features with row stride {guider.Fld} / {actor.Fld}, "
-                             f"the env provides {F} with row stride {self.Fld}")
+        nets = [n for n in (guider, actor) if n is not None]
+        if any(n.F != F or n.Fld != self.Fld for n in nets):
+            raise ValueError(f"networks built for {' / '.join(str(n.F) for n in nets)} observation features with row stride "
+                             f"{' / '.join(str(n.Fld) for n in nets)}, the env provides {F} with row stride {self.Fld}")
         self.guider, self.actor = guider, actor
-        self.g_opt, self.a_opt = optims if optims is not None else (ClipAdam(guider, sys), ClipAdam(actor, sys))
-        assert self.g_opt.net is guider and self.a_opt.net is actor
+        self.g_opt, self.a_opt = optims if optims is not None else (ClipAdam(guider, sys), ClipAdam(actor, sys) if actor is not None else None)
+        assert self.g_opt.net is guider and (self.a_opt is None or self.a_opt.net is actor)
         self.sable_action_select_fn, self.sable_apply_fn, self.actor_apply_fn = apply_fns if apply_fns is not None else \
-            (guider.get_actions, guider.apply, actor.apply)
-        self.sable_update_fn, self.actor_update_fn = update_fns if update_fns is not None else (self.g_opt.update, self.a_opt.update)
-        self.loss_out = self.grad_all[gn + an:gn + an + 9]
+            (guider.get_actions, guider.apply, actor.apply if actor is not None else None)
+        self.sable_update_fn, self.actor_update_fn = update_fns if update_fns is not None else \
+            (self.g_opt.update, self.a_opt.update if self.a_opt is not None else None)
+        self.loss_out = self.grad_all[gn + an:gn + an + self.n_loss]
         self.nt = self.guider.ntile
-        self.groups: List[EnvGroup] = [EnvGroup(env_cfg, num_envs, self.T, device, self.nb, self.nt) for _ in range(num_groups)]
+        self.groups: List[EnvGroup] = [EnvGroup(env_cfg, num_envs, self.T, device, self.nb, self.nt, policy=self.has_actor)
+                                       for _ in range(num_groups)]
         # rollout-start states of all groups in ONE tensor each (group g = envs g*N .. g*N + N - 1), so that the minibatches of all
         # local groups train as one batch of sequences (update(): the groups differ only in their advantage statistics)
         U_, N_ = num_groups, num_envs
         self._prev_hs = tuple(torch.zeros(self.nb, self.nt, U_ * N_, 64, 64, device=device) for _ in range(3))
-        self._policy_h0 = torch.zeros(U_ * N_ * A, 128, device=device)
+        self._policy_h0 = torch.zeros(U_ * N_ * A, 128, device=device) if self.has_actor else None
         for gi, g in enumerate(self.groups):
             g.prev_sable_hs = tuple(t[:, :, gi * N_:(gi + 1) * N_] for t in self._prev_hs)
-            g.policy_h0 = self._policy_h0[gi * N_ * A:(gi + 1) * N_ * A]
+            if self.has_actor:
+                g.policy_h0 = self._policy_h0[gi * N_ * A:(gi + 1) * N_ * A]
         f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=device)
         # optimiser state (optax adam: count, mu, nu) lives in the two ClipAdam objects: g_mu / g_nu / g_count ... below are views of it
         self.ws64 = torch.zeros(8 * 1024, dtype=torch.float64, device=device)
@@ -215,7 +227,8 @@ class MagpoLearner:
             g.key = ks[1].copy()
             for h in g.sable_hs:
                 h.zero_()
-            g.policy_h[0].zero_()
+            if self.has_actor:
+                g.policy_h[0].zero_()
             g.cur = 0
 
     # ------------------------------------------------------------------ rollout (rec_magpo.py:126-212)
@@ -303,9 +316,10 @@ class MagpoLearner:
         tr = g.traj
         for d, s in zip(g.prev_sable_hs, g.sable_hs):
             d.copy_(s)
-        g.policy_h0.copy_(g.policy_h[g.cur])
+        if self.has_actor:
+            g.policy_h0.copy_(g.policy_h[g.cur])
         main = torch.cuda.current_stream()
-        side = self._actor_stream if self.overlap_actor_step else None
+        side = self._actor_stream if self.overlap_actor_step and self.has_actor else None
         fused = self.fused_act
         gtag = str(self.groups.index(g))
         act = (lambda *a, **k: self.sable_action_select_fn(*a, tag=gtag, **k)) if fused else self.guider.act
@@ -317,7 +331,7 @@ class MagpoLearner:
 
         for t in range(T):
             obs, pos, done_prev = self._net_view(tr["obs"][t]), tr["step_count"][t], tr["done"][t]
-            if not self.batched_actor_carry:
+            if self.has_actor and not self.batched_actor_carry:
                 # the actor's hidden-state carry is a pure function of (obs, done); per step it can run on a side stream
                 h_in, h_out = g.policy_h[g.cur], g.policy_h[1 - g.cur]
                 if side is not None:
@@ -341,7 +355,7 @@ class MagpoLearner:
                 zero_done(tr["done"][t + 1])
         if side is not None:
             main.wait_stream(side)
-        if self.batched_actor_carry:   # one scan over the finished trajectory instead of T single steps (same result)
+        if self.has_actor and self.batched_actor_carry:   # one scan over the finished trajectory instead of T single steps (same result)
             ccl = None
             if self.class_tables:   # input side of the GRU on the A*maxval distinct (agent, target) rows
                 if getattr(g, "traj_cls", None) is None:
@@ -395,18 +409,18 @@ class MagpoLearner:
             f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.dev)
             i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=self.dev)
             m.update(R=R, obs=f32(R, F), action=i32(R), prev=i32(R), pos=i32(R), done=torch.empty(U * mb, T, dtype=torch.uint8, device=self.dev),
-                     value=f32(R), logp=f32(R), adv=f32(R), targets=f32(R), h0idx=i32(U * mb * A),
-                     dg=f32(R, 64), da=f32(R, 64), dv=f32(R),
+                     value=f32(R), logp=f32(R), adv=f32(R), targets=f32(R), h0idx=i32(U * mb * A) if self.has_actor else None,
+                     dg=f32(R, 64), da=f32(R, 64) if self.has_actor else None, dv=f32(R),
                      mask=torch.empty(R, K, dtype=torch.uint8, device=self.dev) if self.env_cfg.has_mask else None)
         for u, gi in enumerate(groups):
             tr = self.groups[gi].traj
             r = slice(u * R1, (u + 1) * R1)
-            h0 = m["h0idx"][u * mb * A:(u + 1) * mb * A]
+            h0 = m["h0idx"][u * mb * A:(u + 1) * mb * A] if self.has_actor else None   # start-state rows of the GRU actor
             self.L.call("magpo_gather_minibatch", tr["obs"], tr["action"], tr["step_count"], tr["done"], tr["mask"], tr["value"], tr["log_prob"],
                         tr["adv"], tr["targets"], env_idx, agent_perm, m["obs"][r], m["action"][r], m["prev"][r], m["pos"][r],
                         m["done"][u * mb:(u + 1) * mb], None if m["mask"] is None else m["mask"][r], m["value"][r], m["logp"][r], m["adv"][r], m["targets"][r], h0, T, N, A, F, K, mb,
                         self._st())
-            if gi:
+            if gi and h0 is not None:
                 h0.add_(gi * N * A)      # rows of the stacked start states
         return m
 
@@ -419,7 +433,8 @@ class MagpoLearner:
                      pos_enc=torch.empty(Ce, dtype=torch.int32, device=self.dev), prev_dec=torch.empty(Cd, dtype=torch.int32, device=self.dev),
                      pos_dec=torch.empty(Cd, dtype=torch.int32, device=self.dev))
             self.L.call("magpo_coordsum_class_rows", A, mv, npos, K, c["obs_enc"], c["pos_enc"], c["prev_dec"], c["pos_dec"], self._st())
-            c["obs_act"] = c["obs_enc"][::npos].contiguous()     # actor class (agent, target) = encoder class // npos
+            if self.has_actor:
+                c["obs_act"] = c["obs_enc"][::npos].contiguous()     # actor class (agent, target) = encoder class // npos
             c["zero"] = torch.zeros(1, dtype=torch.int64, device=self.dev)
             self._cls = c
         return self._cls
@@ -442,6 +457,8 @@ class MagpoLearner:
                 c["bounds_" + side] = torch.arange(C + 1, dtype=torch.int32, device=self.dev)
             offsets = torch.searchsorted(vals, c["bounds_" + side])
             out[side] = (cls, order, offsets)
+        if not self.has_actor:
+            return out
         cls_act = torch.div(m["cls_enc"], c["npos"], rounding_mode="floor").to(torch.int32)
         out["act"] = (c["obs_act"], cls_act, out["enc"][1], out["enc"][2][::c["npos"]].contiguous())
         return out
@@ -466,19 +483,9 @@ class MagpoLearner:
         ``hs_idx`` [mb]: env whose rollout-start Sable states sequence j trains on (quirk B19: in the reference
         it differs from ``env_idx`` after the first PPO epoch); default = ``env_idx``.  ``adv_stats`` [U, 2]: advantage statistics to
         use instead of those of the rows at hand (micro-batches: the statistics of the whole minibatch)."""
-        s, T, A, K, N = self.sys, self.T, self.A, self.K, self.N
-        groups = [group] if isinstance(group, int) else list(group)
-        U = len(groups)
-        m = self._gather(groups, env_idx, agent_perm)
-        mb, R = env_idx.numel(), m["R"]
-        nseq, R1 = U * mb, R // U
-        hidx = env_idx if hs_idx is None else hs_idx
-        if U > 1 or groups[0]:
-            hidx = torch.cat([hidx + gi * N for gi in groups])
-        cl = self._classes(m) if self.class_tables else None
-        acl = None if cl is None else cl["act"]
-        gcl = None if cl is None else dict(rows=(self._cls["obs_enc"], self._cls["pos_enc"], self._cls["prev_dec"], self._cls["pos_dec"]),
-                                           enc=cl["enc"], dec=cl["dec"])
+        s, T, K = self.sys, self.T, self.K
+        m, hidx, U, gcl, acl = self._minibatch_inputs(env_idx, agent_perm, group, hs_idx)
+        R, nseq = m["R"], U * env_idx.numel()
         side = self._actor_stream if self.overlap_actor else None
         main = torch.cuda.current_stream()
         if side is not None:
@@ -491,6 +498,39 @@ class MagpoLearner:
         else:
             a_logits = self.actor_apply_fn(self._net_view(m["obs"]), m["done"], self._policy_h0, m["h0idx"], nseq, T, classes=acl)
         st = self._st()
+        stats = self._minibatch_stats(m, U, adv_stats)
+        self.L.call("magpo_loss_fwd_bwd", g_logits, 64, a_logits, 64, m["mask"], m["action"], m["logp"], m["value"], value, m["adv"], m["targets"],
+                    stats, m["dg"], 64, m["da"], 64, m["dv"], self.ws64, self.loss_out, R, K, s.clip_eps, s.clip_gpo,
+                    s.ent_coef, s.vf_coef, s.alpha, st)
+        if side is not None:
+            side.wait_stream(main)  # loss gradients are ready
+            with torch.cuda.stream(side):
+                self.actor.seq_bwd(m["da"])
+        self.guider.train_bwd(m["dg"], m["dv"])
+        if side is not None:
+            main.wait_stream(side)
+        else:
+            self.actor.seq_bwd(m["da"])
+
+    def _minibatch_inputs(self, env_idx: torch.Tensor, agent_perm: torch.Tensor, group, hs_idx: Optional[torch.Tensor]):
+        """What every system's minibatch starts from: the gathered rows, the start-state rows of their sequences, the number of groups
+        in the batch and the (guider, actor) class tables."""
+        groups = [group] if isinstance(group, int) else list(group)
+        U = len(groups)
+        m = self._gather(groups, env_idx, agent_perm)
+        hidx = env_idx if hs_idx is None else hs_idx
+        if U > 1 or groups[0]:
+            hidx = torch.cat([hidx + gi * self.N for gi in groups])
+        cl = self._classes(m) if self.class_tables else None
+        acl = None if cl is None or not self.has_actor else cl["act"]
+        gcl = None if cl is None else dict(rows=(self._cls["obs_enc"], self._cls["pos_enc"], self._cls["prev_dec"], self._cls["pos_dec"]),
+                                           enc=cl["enc"], dec=cl["dec"])
+        return m, hidx, U, gcl, acl
+
+    def _minibatch_stats(self, m, U: int, adv_stats: Optional[torch.Tensor]) -> torch.Tensor:
+        """The [mean, 1 / (std + eps)] pair the loss kernel normalises the advantages with (rec_magpo.py:283,356; rec_sable.py:199)."""
+        R, st = m["R"], self._st()
+        R1 = R // U
         if U == 1:
             if adv_stats is None:
                 self.L.call("magpo_adv_moments", m["adv"], R, self.ws64, self.adv_stats, st)
@@ -506,18 +546,7 @@ class MagpoLearner:
             a2 = m["adv"].view(U, R1)
             a2.sub_(su[:, 0:1]).mul_(su[:, 1:2])
             stats = self._adv_ident
-        self.L.call("magpo_loss_fwd_bwd", g_logits, 64, a_logits, 64, m["mask"], m["action"], m["logp"], m["value"], value, m["adv"], m["targets"],
-                    stats, m["dg"], 64, m["da"], 64, m["dv"], self.ws64, self.loss_out, R, K, s.clip_eps, s.clip_gpo,
-                    s.ent_coef, s.vf_coef, s.alpha, st)
-        if side is not None:
-            side.wait_stream(main)  # loss gradients are ready
-            with torch.cuda.stream(side):
-                self.actor.seq_bwd(m["da"])
-        self.guider.train_bwd(m["dg"], m["dv"])
-        if side is not None:
-            main.wait_stream(side)
-        else:
-            self.actor.seq_bwd(m["da"])
+        return stats
 
     def apply_grads(self, grad_scale: float = 1.0):
         """optax clip_by_global_norm + adam + apply_updates on both flat buffers (rec_magpo.py:412-420): the two update functions."""
@@ -526,13 +555,13 @@ class MagpoLearner:
 
     # ------------------------------------------------------------------ update (rec_magpo.py:214-487)
     def update(self, grad_sync: Optional[Callable[["MagpoLearner"], float]] = None) -> torch.Tensor:
-        """ppo_epochs x num_minibatches optimisation steps; returns the loss table [P, M, 9] (device), already
+        """ppo_epochs x num_minibatches optimisation steps; returns the loss table [P, M, n_loss] (device), already
         averaged over groups (and ranks when grad_sync all-reduces)."""
         s, N, A = self.sys, self.N, self.A
         M = s.num_minibatches
         mbs = N // M
         U = len(self.groups)
-        losses = torch.zeros(s.ppo_epochs, M, 9, device=self.dev)
+        losses = torch.zeros(s.ppo_epochs, M, self.n_loss, device=self.dev)
         # Quirk B19 (rec_magpo.py:437,447,471): the reference shuffles prev_hstates by batch_perm and carries the SHUFFLED
         # arrays into the next epoch, so epoch e reads state row hs_idx_e[i] = hs_idx_{e-1}[batch_perm_e[i]] for
         # sequence i while the trajectory is gathered by batch_perm_e alone.  Only the index is composed; the 48 KiB

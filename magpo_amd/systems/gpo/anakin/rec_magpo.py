@@ -39,13 +39,38 @@ from magpo_amd.utils.logger import LogEvent, MavaLogger
 LearnerState = GPOLearnerState
 
 
-def _system_config(config) -> SystemConfig:
+def _system_config(config, clip_gpo=None, alpha=None) -> SystemConfig:
+    """``clip_gpo`` / ``alpha``: given by a system whose config tree has no such keys (rec_sable, which never reads them); rec_magpo's are required."""
     s = config.system
     return SystemConfig(rollout_length=int(s.rollout_length), ppo_epochs=int(s.ppo_epochs), num_minibatches=int(s.num_minibatches),
                         gamma=float(s.gamma), gae_lambda=float(s.gae_lambda), clip_eps=float(s.clip_eps), ent_coef=float(s.ent_coef),
-                        vf_coef=float(s.vf_coef), max_grad_norm=float(s.max_grad_norm), clip_gpo=float(s.clip_gpo),
-                        alpha=float(s.alpha), actor_lr=float(s.actor_lr), decay_learning_rates=bool(s.get("decay_learning_rates", False)),
+                        vf_coef=float(s.vf_coef), max_grad_norm=float(s.max_grad_norm), clip_gpo=float(s.clip_gpo if clip_gpo is None else clip_gpo),
+                        alpha=float(s.alpha if alpha is None else alpha), actor_lr=float(s.actor_lr), decay_learning_rates=bool(s.get("decay_learning_rates", False)),
                         lr_num_updates=int(s.num_updates) if s.get("num_updates") else 1000, micro_batches=int(s.get("micro_batches", 1) or 1))
+
+
+def sable_hstates_logical(gd: SableGuider, t: torch.Tensor) -> torch.Tensor:
+    """Device retention states [n_block, ntile, N, 64, 64] -> the reference's [n_block, n_head, N, hs, hs] head states
+    (get_init_hstates.py:20-43).  On the device a head state sits in a zero-padded 64 x 64 tile, and a narrow net (embed_dim < 64,
+    params.WidthEmbedding) keeps logical entry (i, j) at device rows m i (q / k live in the first copy) and columns m j .. m j + m - 1
+    (v is duplicated), m = 64 / embed_dim.  The one 128-wide head of embed_dim 128 / n_head 1 lives in four 64 x 64 tiles S[I][J] (tile 2 I + J)."""
+    hw, m = gd.hs, max(1, 64 // gd.EL)
+    if gd.blockwise:
+        return torch.cat([torch.cat([t[:, 0], t[:, 1]], -1), torch.cat([t[:, 2], t[:, 3]], -1)], -2).unsqueeze(1)
+    return t[..., :hw:m, :hw:m]
+
+
+def load_sable_hstates(gd: SableGuider, dst: torch.Tensor, logical: torch.Tensor) -> None:
+    """Inverse of ``sable_hstates_logical``: write the logical head states into the device tiles ``dst``."""
+    hw, m = gd.hs, max(1, 64 // gd.EL)
+    dst.zero_()
+    if gd.blockwise:   # [n_block, 1, N, 128, 128] -> tiles (I, J)
+        full = logical[:, 0]
+        for ti in range(4):
+            dst[:, ti].copy_(full[..., 64 * (ti // 2):64 * (ti // 2) + 64, 64 * (ti % 2):64 * (ti % 2) + 64])
+        return
+    for c in range(m):   # rows m i, every column copy
+        dst[..., :hw:m, c:hw:m].copy_(logical)
 
 
 def _snapshot_state(learner: MagpoLearner) -> GPOLearnerState:
@@ -56,18 +81,9 @@ def _snapshot_state(learner: MagpoLearner) -> GPOLearnerState:
     params = Params({k: v.clone() for k, v in learner.guider.named.items()}, {k: v.clone() for k, v in learner.actor.named.items()})
     opt = OptStates(dict(count=learner.g_count, mu=learner.g_mu.clone(), nu=learner.g_nu.clone()),
                     dict(count=learner.a_count, mu=learner.a_mu.clone(), nu=learner.a_nu.clone()))
-    # The state carries the reference's [embed_dim / n_head, embed_dim / n_head] head states (get_init_hstates.py:20-43).  On the
-    # device a head state sits in a zero-padded 64 x 64 tile, and a narrow net (embed_dim < 64, params.WidthEmbedding) keeps logical
-    # entry (i, j) at device rows m i (q / k live in the first copy) and columns m j .. m j + m - 1 (v is duplicated), m = 64 / embed_dim.
-    # The one 128-wide head of embed_dim 128 / n_head 1 lives in four 64 x 64 tiles S[I][J] (tile 2 I + J).
+    # The state carries the reference's [embed_dim / n_head, embed_dim / n_head] head states (sable_hstates_logical)
     gd = learner.guider
-    hw, m = gd.hs, max(1, 64 // gd.EL)
-
-    def logical(t):   # [n_block, ntile, N, 64, 64] -> [n_block, n_head, N, hs_logical, hs_logical]
-        if gd.blockwise:
-            return torch.cat([torch.cat([t[:, 0], t[:, 1]], -1), torch.cat([t[:, 2], t[:, 3]], -1)], -2).unsqueeze(1)
-        return t[..., :hw:m, :hw:m]
-    hs = HiddenStates(SableHiddenStates(*[torch.stack([logical(g.sable_hs[i]) for g in gs]) for i in range(3)]),
+    hs = HiddenStates(SableHiddenStates(*[torch.stack([sable_hstates_logical(gd, g.sable_hs[i]) for g in gs]) for i in range(3)]),
                       torch.stack([g.policy_h[g.cur] for g in gs]))
     env_state = {f: torch.stack([getattr(g.env, f) for g in gs]) for f in gs[0].env.state_fields}
     timestep = dict(agents_view=torch.stack([g.traj["obs"][0] for g in gs]), step_count=torch.stack([g.traj["step_count"][0] for g in gs]))
@@ -98,17 +114,8 @@ def load_learner_state(learner: MagpoLearner, state: GPOLearnerState) -> None:
             grp.traj["mask"][0].copy_(state.timestep["action_mask"][gi])
         grp.traj["step_count"][0].copy_(state.timestep["step_count"][gi])
         grp.traj["done"][0].copy_(state.dones[gi])
-        gd = learner.guider
-        hw, m = gd.hs, max(1, 64 // gd.EL)
         for i in range(3):
-            grp.sable_hs[i].zero_()
-            if gd.blockwise:   # [n_block, 1, N, 128, 128] -> tiles (I, J)
-                full = sable[i][gi][:, 0]
-                for ti in range(4):
-                    grp.sable_hs[i][:, ti].copy_(full[..., 64 * (ti // 2):64 * (ti // 2) + 64, 64 * (ti % 2):64 * (ti % 2) + 64])
-                continue
-            for c in range(m):   # rows m i, every column copy (inverse of the collapse in _snapshot_state)
-                grp.sable_hs[i][..., :hw:m, c:hw:m].copy_(sable[i][gi])
+            load_sable_hstates(learner.guider, grp.sable_hs[i], sable[i][gi])
         grp.policy_h[grp.cur].copy_(hst["policy_hidden_state"][gi])
         grp.key = np.array(state.key, dtype=np.uint32).copy()
 
@@ -166,9 +173,17 @@ def get_learner_fn(env, apply_fns, update_fn, config):
                            apply_fns=tuple(apply_fns), update_fns=tuple(update_fn))
     grad_sync = mdist.make_grad_sync(world)   # the pmean over ("batch", "device") of rec_magpo.py:395-409: one all-reduce of the flat buffer
 
-    def learner_fn(learner_state: GPOLearnerState) -> ExperimentOutput:
+    return make_learner_fn(learner, config, grad_sync, _snapshot_state, load_learner_state,
+                           ["total_loss", "value_loss", "actor_loss", "guider_loss", "kl_loss", "entropy"])
+
+
+def make_learner_fn(learner, config, grad_sync, snapshot, load, loss_names):
+    """``learn(learner_state) -> ExperimentOutput`` around a learner object: ``config.system.num_updates_per_eval`` update steps, the
+    per-step episode metrics and the loss table under ``loss_names`` (the first columns of the learner's loss scalars).  ``snapshot`` /
+    ``load`` turn the learner's device buffers into the system's LearnerState and back.  Shared by the systems (rec_magpo, rec_sable)."""
+    def learner_fn(learner_state) -> ExperimentOutput:
         if learner_state is not getattr(learner, "_live_state", None):
-            load_learner_state(learner, learner_state)
+            load(learner, learner_state)
         n_up = int(config.system.num_updates_per_eval)
         # linear_scedule reads config.system.num_updates when the learner is traced, i.e. at the first learn() call -- AFTER
         # check_total_timesteps has rewritten it on the same config object (mava/utils/training.py:37-43; rec_magpo.py:581 vs :717)
@@ -180,12 +195,11 @@ def get_learner_fn(env, apply_fns, update_fn, config):
             train.append(losses)
             for k in ep:
                 ep[k].append(torch.stack([g.metrics[k] for g in learner.groups]).cpu().numpy())
-        tl = torch.stack(train).cpu().numpy()  # (updates, P, M, 9)
-        names = ["total_loss", "value_loss", "actor_loss", "guider_loss", "kl_loss", "entropy"]
-        train_metrics = {n: tl[..., i] for i, n in enumerate(names)}
+        tl = torch.stack(train).cpu().numpy()  # (updates, P, M, n_loss)
+        train_metrics = {n: tl[..., i] for i, n in enumerate(loss_names)}
         episode_metrics = {k: np.stack(v) for k, v in ep.items()}
         episode_metrics["is_terminal_step"] = episode_metrics["is_terminal_step"].astype(bool)
-        learner._live_state = _snapshot_state(learner)
+        learner._live_state = snapshot(learner)
         return ExperimentOutput(learner._live_state, episode_metrics, train_metrics)
 
     learner_fn.learner = learner
@@ -255,7 +269,6 @@ def run_experiment(_config) -> float:
     rank, world, local = mdist.init_from_env()
     torch.cuda.set_device(local)
     device = torch.device("cuda", local)
-    n_devices = world
 
     env, eval_env = environments.make(config)
     ks = host_split(prng_key(int(config.system.seed)), 4)
@@ -266,6 +279,17 @@ def run_experiment(_config) -> float:
     eval_actor = GruActor(env.num_agents, env.action_dim, env.obs_dim, device, obs_ld=obs_row_stride(env.cfg.obs_dim),
                           pre_torso=actor_network.pre_spec, post_torso=actor_network.post_spec)
     eval_act_fn = make_rec_eval_act_fn(eval_actor, config)
+    return train_and_evaluate(config, env, eval_env, learn, learner_state, eval_act_fn, key, key_e, device, rank, world,
+                              init_act_state=lambda batch: {"hidden_state": torch.zeros(batch * env.num_agents, 128, device=device)},
+                              eval_params=lambda state: state.params.actor_params)
+
+
+def train_and_evaluate(config, env, eval_env, learn, learner_state, eval_act_fn, key, key_e, device, rank, world, *, init_act_state, eval_params) -> float:
+    """The experiment loop both systems run after their set-up (rec_magpo.py:702-815, rec_sable.py:518-620): evaluator, timestep
+    bookkeeping, logger, checkpoint save / resume, ``num_evaluation`` x (learn, evaluate the pre-interval parameters), absolute metric.
+    ``init_act_state(batch)``: the evaluator's initial actor state for ``batch`` envs; ``eval_params(learner_state)``: the parameter
+    dict the act function evaluates."""
+    n_devices = world
     evaluator = get_eval_fn(eval_env, eval_act_fn, config, absolute_metric=False, device=device, n_devices=n_devices)
 
     config = check_total_timesteps(config, n_devices)
@@ -296,7 +320,7 @@ def run_experiment(_config) -> float:
     else:
         resume = {}
     eval_batch = get_num_eval_envs(config, absolute_metric=False, n_devices=n_devices)
-    eval_hs = {"hidden_state": torch.zeros(eval_batch * env.num_agents, 128, device=device)}
+    eval_hs = init_act_state(eval_batch)
 
     max_episode_return = -np.inf
     best_params = None
@@ -323,7 +347,7 @@ def run_experiment(_config) -> float:
                             "steps_per_second": steps_per_rollout / elapsed}, t, eval_step, LogEvent.ACT)
             logger.log(learner_output.train_metrics, t, eval_step, LogEvent.TRAIN)
         # evaluate the PRE-interval actor parameters, as the reference does (rec_magpo.py:770)
-        trained_params = learner_state.params.actor_params
+        trained_params = eval_params(learner_state)
         ks = host_split(key_e, n_devices + 1)
         key_e, eval_key = ks[0], ks[1 + rank]
         eval_metrics = evaluator(trained_params, eval_key, eval_hs)
@@ -345,7 +369,7 @@ def run_experiment(_config) -> float:
     eval_performance = float(np.mean(eval_metrics[config.env.eval_metric])) if eval_metrics else float("nan")
     if config.arch.absolute_metric:
         eb = get_num_eval_envs(config, absolute_metric=True, n_devices=n_devices)
-        abs_hs = {"hidden_state": torch.zeros(eb * env.num_agents, 128, device=device)}
+        abs_hs = init_act_state(eb)
         abs_eval = get_eval_fn(eval_env, eval_act_fn, config, absolute_metric=True, device=device, n_devices=n_devices)
         abs_key = host_split(key, n_devices)[rank]
         m = abs_eval(best_params, abs_key, abs_hs)

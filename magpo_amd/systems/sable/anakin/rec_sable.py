@@ -1,0 +1,218 @@
+"""Sable system entry point on MI355X -- drop-in for mava/systems/sable/anakin/rec_sable.py: the guider of MAGPO trained alone with PPO.
+
+Same public names and call contract as the reference system file:
+    hydra_entry_point / main(overrides)      rec_sable.py:623-636
+    run_experiment(config) -> float          rec_sable.py:481-620   (make_rec_sable_act_fn :498-513)
+    learner_setup(env, keys, config) -> (learn, sable_execution_fn, init_learner_state)   rec_sable.py:351-478
+    get_learner_fn(env, apply_fns, update_fn, config) -> LearnerFn                        rec_sable.py:53-348
+The bodies drive the HIP kernels (magpo_amd.sable_learner.SableLearner); the experiment loop, the learner loop and the state layout
+helpers are the ones rec_magpo uses.
+
+    python -m magpo_amd.systems.sable.anakin.rec_sable env=coordsum env/scenario=3x30-50 arch.num_envs=64
+"""
+from __future__ import annotations
+
+import copy
+import sys
+from typing import Callable, Dict, List, Optional
+
+import numpy as np
+import torch
+
+from magpo_amd import distributed as mdist
+from magpo_amd.config import compose
+from magpo_amd.learner import SystemConfig, host_split, obs_row_stride, prng_key
+from magpo_amd.optim import ClipAdam
+from magpo_amd.sable import SableGuider
+from magpo_amd.sable_learner import LOSS_NAMES, SableLearner
+from magpo_amd.systems.gpo.anakin.rec_magpo import (_owner, _system_config, load_sable_hstates, make_learner_fn, sable_hstates_logical,
+                                                    train_and_evaluate)
+from magpo_amd.systems.sable.types import HiddenStates, LearnerState, Transition  # noqa: F401
+from magpo_amd.types import ExperimentOutput  # noqa: F401
+from magpo_amd.utils import make_env as environments
+
+
+def system_config(config) -> SystemConfig:
+    """The learner's settings from a rec_sable config tree: it has no ``clip_gpo`` / ``alpha`` (MAGPO's keys, which rec_magpo requires and
+    this system never reads), so they take SystemConfig's defaults."""
+    return _system_config(config, clip_gpo=SystemConfig.clip_gpo, alpha=SystemConfig.alpha)
+
+
+def _snapshot_state(learner: SableLearner) -> LearnerState:
+    """LearnerState of the learner as an independent COPY (rec_sable.py:309-316); leaves carry a leading group axis.  ``timestep``
+    holds what the next rollout reads of the reference's TimeStep: the observation and ``last`` (= timestep.last(), the done flag
+    the first transition records, rec_sable.py:112)."""
+    gs, gd = learner.groups, learner.guider
+    params = {k: v.clone() for k, v in gd.named.items()}
+    opt = dict(count=learner.g_count, mu=learner.g_mu.clone(), nu=learner.g_nu.clone())
+    hs = HiddenStates(*[torch.stack([sable_hstates_logical(gd, g.sable_hs[i]) for g in gs]) for i in range(3)])
+    env_state = {f: torch.stack([getattr(g.env, f) for g in gs]) for f in gs[0].env.state_fields}
+    timestep = dict(agents_view=torch.stack([g.traj["obs"][0] for g in gs]), step_count=torch.stack([g.traj["step_count"][0] for g in gs]),
+                    last=torch.stack([g.traj["done"][0] for g in gs]))
+    if gs[0].traj["mask"] is not None:
+        timestep["action_mask"] = torch.stack([g.traj["mask"][0] for g in gs])
+    return LearnerState(params, opt, gs[0].key.copy(), env_state, timestep, hs)
+
+
+def load_learner_state(learner: SableLearner, state: LearnerState) -> None:
+    """Inverse of ``_snapshot_state``: write every leaf of ``state`` into the learner's (static, graph-captured) buffers."""
+    as_dict = lambda x: x if isinstance(x, dict) else x._asdict()
+    learner.guider.load_named(state.params)
+    opt = state.opt_states
+    learner.g_mu.copy_(opt["mu"]); learner.g_nu.copy_(opt["nu"]); learner.g_count = int(opt["count"])
+    hst = as_dict(state.hstates)
+    sable = (hst["encoder"], hst["decoder_self_retn"], hst["decoder_cross_retn"])
+    if state.timestep["last"].shape[0] != len(learner.groups):
+        raise ValueError(f"learner state holds {state.timestep['last'].shape[0]} env groups, the learner {len(learner.groups)}")
+    for gi, grp in enumerate(learner.groups):
+        for f in grp.env.state_fields:
+            getattr(grp.env, f).copy_(state.env_state[f][gi])
+        grp.traj["obs"][0].copy_(state.timestep["agents_view"][gi])
+        if grp.traj["mask"] is not None:
+            grp.traj["mask"][0].copy_(state.timestep["action_mask"][gi])
+        grp.traj["step_count"][0].copy_(state.timestep["step_count"][gi])
+        grp.traj["done"][0].copy_(state.timestep["last"][gi])
+        for i in range(3):
+            load_sable_hstates(learner.guider, grp.sable_hs[i], sable[i][gi])
+        grp.key = np.array(state.key, dtype=np.uint32).copy()
+
+
+def get_learner_fn(env, apply_fns, update_fn, config):
+    """Returns ``learn(learner_state) -> ExperimentOutput``: ``config.system.num_updates_per_eval`` update steps (rec_sable.py:53-348).
+
+        apply_fns = (sable_action_select_fn, sable_apply_fn)     rec_sable.py:62   (execution / training)
+        update_fn = the optimiser's update function              rec_sable.py:56
+
+    As in the MAGPO system the callables must be methods of the objects that own the device buffers -- ``SableGuider.get_actions``,
+    ``SableGuider.apply`` and ``ClipAdam.update``, or thin ``functools.wraps`` / ``functools.partial`` adaptors around them -- and the
+    loop CALLS exactly what it is given; anything else raises the ``TypeError`` of rec_magpo._owner.  State in, state out: a state
+    other than the last one produced is loaded into the buffers first, so ``learn`` is a function of its argument."""
+    sable_action_select_fn, sable_apply_fn = apply_fns
+    guider = _owner(sable_apply_fn, SableGuider, "apply", "apply_fns[1] (sable_apply_fn)")
+    if _owner(sable_action_select_fn, SableGuider, "get_actions", "apply_fns[0] (sable_action_select_fn)") is not guider:
+        raise ValueError("the execution and the training function must belong to one Sable network")
+    optim = _owner(update_fn, ClipAdam, "update", "update_fn")
+    _, world = mdist.rank_world()
+    learner = SableLearner(env.cfg, int(config.arch.num_envs), optim.sys, guider.dev, num_groups=int(config.system.update_batch_size),
+                           guider=guider, optim=optim, apply_fns=tuple(apply_fns), update_fn=update_fn)
+    grad_sync = mdist.make_grad_sync(world)   # the two pmeans of rec_sable.py:242-244: one all-reduce of [gradients | 4 loss scalars]
+    return make_learner_fn(learner, config, grad_sync, _snapshot_state, load_learner_state, list(LOSS_NAMES))
+
+
+def learner_setup(env, keys, config, device=None, rank: int = 0, world: int = 1):
+    """Initialise learner_fn, network, optimiser, environments and states (rec_sable.py:351-478)."""
+    key, net_key = keys
+    config.system.num_agents = env.num_agents
+    nc, mc = config.network.net_config, config.network.memory_config
+    # chunk size: a memory / speed knob of the reference's chunkwise evaluation with no effect on the function (see rec_magpo.learner_setup)
+    if mc.timestep_chunk_size:
+        mc.chunk_size = int(mc.timestep_chunk_size) * env.num_agents
+    else:
+        mc.chunk_size = config.system.rollout_length * env.num_agents
+    if mc.type != "rec_sable":
+        raise NotImplementedError("memory_config.type must be rec_sable")
+    if int(nc.embed_dim) not in (16, 32, 64, 128) or int(nc.n_head) not in (1, 2, 4):
+        raise NotImplementedError("HIP kernels support embed_dim in {16,32,64,128}, n_head in {1,2,4} (any n_block)")
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    U = int(config.system.update_batch_size)
+    cfg, sysc = env.cfg, system_config(config)
+    # parameters = what flax creates from net_key (rec_sable.py:403-409; magpo_amd/params.py)
+    sable_network = SableGuider(cfg.num_agents, cfg.num_actions, env.obs_dim, device, obs_ld=obs_row_stride(cfg.obs_dim), embed_dim=int(nc.embed_dim),
+                                n_head=int(nc.n_head), n_block=int(nc.n_block), decay_scaling_factor=float(mc.decay_scaling_factor),
+                                use_pe=bool(mc.timestep_positional_encoding), max_pos=cfg.time_limit + 1, seed=np.asarray(net_key, np.uint32))
+    optim = ClipAdam(sable_network, sysc)
+    apply_fns = (sable_network.get_actions, sable_network.apply)   # execution function, training function (rec_sable.py:413-416)
+    learn = get_learner_fn(env, apply_fns, optim.update, config)
+    learner = learn.learner
+    learner.setup(key, n_groups=world * U, group=rank * U)
+    learner._live_state = _snapshot_state(learner)
+    return learn, apply_fns[0], learner._live_state
+
+
+def get_init_hidden_state(sable_network: SableGuider, batch_size: int) -> torch.Tensor:
+    """Zero Sable hidden states of the evaluator's act function for ``batch_size`` envs: the three retention states (encoder, decoder
+    self, decoder cross) stacked in one tensor [3, n_block, n_tile, batch, 64, 64] -- the device layout, so that an evaluation step
+    converts nothing (the evaluator clones and carries it as one leaf)."""
+    return torch.zeros(3, sable_network.nb, sable_network.ntile, batch_size, 64, 64, device=sable_network.dev)
+
+
+def make_rec_sable_act_fn(actor_apply_fn: Callable) -> Callable:
+    """``EvalActFn(params, timestep, key, actor_state) -> (action, actor_state)`` that executes the Sable network itself
+    (rec_sable.py:498-513).  ``actor_apply_fn``: ``SableGuider.get_actions`` of the network that evaluates (its own object, so that
+    loading the evaluated parameters does not touch the learner's); ``actor_state`` = {"hidden_state": get_init_hidden_state(...)} for
+    the evaluator's own env batch.  As in the reference the action is always SAMPLED from ``key`` (get_actions has no greedy mode:
+    ``arch.evaluation_greedy`` does not apply to this act function) and the hidden state is carried through an episode end unchanged
+    (the evaluator reads the metrics of every env's first terminal step only).
+    The hidden state is advanced in place and handed back: the caller's tensor is the carried state (get_eval_fn clones its initial
+    state once per episode loop).  Parameters are loaded when a DIFFERENT dict object arrives than the last one: a caller that rewrites
+    the tensors of the same dict in place and passes it again evaluates the previously loaded weights -- pass a new dict (a learner
+    state snapshot is one) or ``net.named`` itself."""
+    net = _owner(actor_apply_fn, SableGuider, "get_actions", "actor_apply_fn")
+    loaded = {"params": None}
+    bufs: Dict[int, Dict[str, torch.Tensor]] = {}
+    _hidden_state = "hidden_state"
+
+    def eval_act_fn(params: Optional[Dict[str, torch.Tensor]], timestep, key: np.ndarray, actor_state):
+        if params is not None and params is not net.named and params is not loaded["params"]:
+            net.load_named(params)
+            loaded["params"] = params
+        ob = timestep.observation
+        view, N, A = ob.agents_view, ob.agents_view.shape[0], net.A
+        io = bufs.get(N)
+        if io is None:   # the kernel's inputs and outputs for this batch size, allocated once (the acting kernel caches its pointer tables)
+            dev = view.device
+            io = bufs[N] = dict(obs=torch.zeros(N, A, net.Fld, device=dev), pos=torch.empty(N, dtype=torch.int32, device=dev),
+                                mask=torch.empty(N, A, net.K, dtype=torch.uint8, device=dev), action=torch.empty(N, A, dtype=torch.int32, device=dev),
+                                logp=torch.empty(N, A, device=dev), value=torch.empty(N, A, device=dev))
+        io["obs"][..., :view.shape[2]].copy_(view)
+        io["pos"].copy_(ob.step_count[:, 0] if ob.step_count.dim() == 2 else ob.step_count)
+        mask = None
+        if ob.action_mask is not None:
+            mask = io["mask"].copy_(ob.action_mask)
+        hs = actor_state[_hidden_state]   # advanced IN PLACE (the acting kernel updates the states where they are)
+        # key, sample_key = split(key) per agent inside get_actions (decode.py:141)
+        keys = np.zeros((A, 2), np.uint32)
+        k = np.asarray(key, dtype=np.uint32).reshape(2)
+        for i in range(A):
+            kk = host_split(k, 2)
+            k, keys[i] = kk[0], kk[1]
+        actor_apply_fn(io["obs"], io["pos"], (hs[0], hs[1], hs[2]), keys, io["action"], io["logp"], io["value"], mask=mask, tag=f"eval{N}")
+        return io["action"].clone(), {_hidden_state: hs}
+
+    return eval_act_fn
+
+
+def run_experiment(_config) -> float:
+    """Runs experiment (rec_sable.py:481-620)."""
+    _config.logger.system_name = "rec_sable"
+    config = copy.deepcopy(_config)
+    rank, world, local = mdist.init_from_env()
+    torch.cuda.set_device(local)
+    device = torch.device("cuda", local)
+
+    env, eval_env = environments.make(config)
+    ks = host_split(prng_key(int(config.system.seed)), 3)
+    key, key_e, net_key = ks[0], ks[1], ks[2]
+    learn, sable_execution_fn, learner_state = learner_setup(env, (key, net_key), config, device, rank, world)
+
+    # the evaluator runs the Sable network on its own batch of envs, with the pre-interval parameters: a second network object
+    train_net = learn.learner.guider
+    eval_net = SableGuider(train_net.A, train_net.K, train_net.F, device, obs_ld=train_net.Fld, embed_dim=train_net.EL, n_head=train_net.nh,
+                           n_block=train_net.nb, decay_scaling_factor=float(config.network.memory_config.decay_scaling_factor),
+                           use_pe=bool(config.network.memory_config.timestep_positional_encoding), max_pos=train_net.npos, tuning=train_net.tuning)
+    eval_act_fn = make_rec_sable_act_fn(eval_net.get_actions)
+    return train_and_evaluate(config, env, eval_env, learn, learner_state, eval_act_fn, key, key_e, device, rank, world,
+                              init_act_state=lambda batch: {"hidden_state": get_init_hidden_state(eval_net, batch)},
+                              eval_params=lambda state: state.params)
+
+
+def hydra_entry_point(overrides: Optional[List[str]] = None) -> float:
+    """Experiment entry point (rec_sable.py:623-636): compose configs/default/rec_sable.yaml + CLI overrides."""
+    cfg = compose("rec_sable", sys.argv[1:] if overrides is None else overrides)
+    perf = run_experiment(cfg)
+    print("Rec Sable experiment completed")
+    return perf
+
+
+if __name__ == "__main__":
+    hydra_entry_point()

@@ -51,7 +51,8 @@ def _rank_path(path: str, rank: int) -> str:
     return path if rank == 0 else path[:-3] + f".rank{rank}.pt"
 
 
-ROLLOUT_FIELDS = ("key", "env_state", "timestep", "dones", "hstates")   # what differs between ranks (params / opt_states are replicated)
+# what differs between ranks (params / opt_states are replicated); the Sable system's state has no "dones" (its timestep carries last())
+ROLLOUT_FIELDS = ("key", "env_state", "timestep", "dones", "hstates")
 
 
 class Checkpointer:
@@ -102,7 +103,7 @@ class Checkpointer:
         path = os.path.join(self.dir, f"{int(timestep)}.pt")
         state = _to_cpu(unreplicated_learner_state)
         if self.rank != 0:
-            _atomic_save({"learner_state": {f: state[f] for f in ROLLOUT_FIELDS}, "timestep": int(timestep), "rank": self.rank},
+            _atomic_save({"learner_state": {f: state[f] for f in ROLLOUT_FIELDS if f in state}, "timestep": int(timestep), "rank": self.rank},
                          _rank_path(path, self.rank))
             return True
         _atomic_save({"learner_state": state, "timestep": int(timestep), "episode_return": float(episode_return), "world": self.world,
@@ -192,7 +193,8 @@ def latest_valid_checkpoint(cdir: str, rank: int = 0, world: int = 1) -> str:
 
 
 def restore_learner_state(path: str, device="cuda", rank: int = 0, world: int = 1):
-    """Load a checkpoint written by ``Checkpointer.save`` and rebuild the full GPOLearnerState on ``device``: parameters,
+    """Load a checkpoint written by ``Checkpointer.save`` and rebuild the full GPOLearnerState (or, for a rec_sable checkpoint, the
+    Sable system's LearnerState) on ``device``: parameters,
     optimiser moments and counters, PRNG key, env state, last timestep / dones and both hidden states -- everything
     ``learn(state)`` needs to continue bit-identically (mava/utils/checkpointing.py:108-145 saves exactly this pytree; the
     reference's own ``restore_params`` :147-198 reads back only params / hidden states).  Rank r > 0 of a multi-rank job takes the
@@ -216,6 +218,10 @@ def restore_learner_state(path: str, device="cuda", rank: int = 0, world: int = 
         return x
 
     hs = st["hstates"]
+    if "dones" not in st:   # the guider-only system (systems/sable/types.py: RecLearnerState)
+        from ..systems.sable.types import HiddenStates as SableHS, LearnerState as SableLearnerState
+        return SableLearnerState(dev(st["params"]), dev(st["opt_states"]), st["key"], dev(st["env_state"]), dev(st["timestep"]),
+                                 SableHS(**dev(hs))), int(ck["timestep"])
     state = GPOLearnerState(Params(dev(st["params"]["guider_params"]), dev(st["params"]["actor_params"])),
                             OptStates(dev(st["opt_states"]["guider_opt_state"]), dev(st["opt_states"]["actor_opt_state"])),
                             st["key"], dev(st["env_state"]), dev(st["timestep"]), dev(st["dones"]),
