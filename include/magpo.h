@@ -131,14 +131,14 @@ int magpo_coordsum_class_rows(int A, int maxval, int npos, int K, float* obs_tab
                               magpo_stream_t stream);
 
 /* ---- dense layers on fp32 MFMA (flax nn.Dense / retention projections) ----
- * act: 0 none, 1 relu, 2 gelu(tanh), 3 swish, 4 mask: Y = (M > 0) ? XW+b : 0 with the mask M passed in the Ypre argument (same stride as Y)
- * -- the ReLU backward fused into dX = dY W^T, 5 tanh, 6 tanh backward: Y = (XW+b) (1 - M^2) with the forward's tanh output M in the Ypre
- * argument (KIN in {64, 128, 192, 256, 384}).  Ypre (act 0-3 and 5, nullable): receives the pre-activation. */
+ * KIN in {64, 128, 192, 256, 384}.  act: 0 none, 1 relu, 2 gelu(tanh), 3 swish, 4 mask: Y = (M > 0) ? XW+b : 0 with the mask M passed in the
+ * mask argument (same stride as Y) -- the ReLU backward fused into dX = dY W^T, 5 tanh, 6 tanh backward: Y = (XW+b) (1 - M^2) with the
+ * forward's tanh output M in the mask argument.  mask is an input, required for act 4 / 6 and null otherwise (MAGPO_EINVAL). */
 /* variant (any other value is MAGPO_EINVAL): linear 0 = fp32 MFMA, 4 = KIN 128 / 192 with at least 128 output columns (four-wave column
  * blocks) on bf16 MFMA with both operands split into three bf16 pieces (24 mantissa bits, six products, fp32 accumulate: fp32 accuracy
  * at 6/16 of the fp32 MFMA time; ignored for other shapes); wgrad 0 = fp32 MFMA, 64 = 128 x 384 with every row tile full on bf16 MFMA
  * with three-piece operand splits (opt-in: faster, but its accumulation error is ~1.2 x the fp32-MFMA kernel's). */
-int magpo_linear(const float* X, int ldx, const float* Wt, const float* bias, float* Y, int ldy, float* Ypre,
+int magpo_linear(const float* X, int ldx, const float* Wt, const float* bias, float* Y, int ldy, float* mask,
                  long R, int KIN, int NOUT, int act, int variant, magpo_stream_t stream);
 int magpo_linear_pro(int pro, const float* a, long lda, const float* y, long ldy_in, const float* s1, const float* s2,
                      const float* pe, const int* pos, long pos_stride, int npos, int use_pe, const float* W,

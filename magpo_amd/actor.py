@@ -177,11 +177,11 @@ class GruActor(NetBase):
 
     def _dx(self, dsrc, ldsrc, W_nat, KIN, NOUT, R, dst, spec, j, rec):
         """dst = dsrc W^T (W in its natural [NOUT, KIN] layout), times the activation derivative of layer j of ``spec`` when that
-        layer has no LayerNorm (fused epilogue: act 4 ReLU mask / act 6 tanh, its output in the Ypre slot)."""
+        layer has no LayerNorm (fused epilogue: act 4 ReLU mask / act 6 tanh, its output as the mask argument)."""
         act, M = 0, None
         if rec[4] is None and spec.act(j):
             act, M = (4 if spec.act(j) == 1 else 6), rec[3]
-        self.lin(dsrc, ldsrc, W_nat, None, dst, NOUT, R, KIN, NOUT, act=act, Ypre=M)
+        self.lin(dsrc, ldsrc, W_nat, None, dst, NOUT, R, KIN, NOUT, act=act, mask=M)
 
     def _wgrad_nrz(self, emb, dg, R, gw, dW, db):
         """dW_i, db_i from dg's columns 0..3H (gate blocks n | r | z) into W_i's order, on the weight-gradient stream."""
@@ -269,7 +269,7 @@ class GruActor(NetBase):
         post, pre, Dq, Dp = sv["post"], sv["pre"], self.Dpost, self.Dpre
         self.wgrad(post[-1][3], Dq, dlogits, 64, R, Dq, K, gv["head.kernel"], gv["head.bias"])
         dy = b.get("g_post_dy", (R, Dq))
-        # dy = dlogits @ W_head^T, masked by the last post-torso layer's activation (fused epilogue: act 4 / 6 take the mask in the Ypre slot)
+        # dy = dlogits @ W_head^T, masked by the last post-torso layer's activation (fused epilogue: act 4 / 6 take it as the mask argument)
         self._dx(dlogits, 64, self.wt["head_nat_pad"], 64, Dq, R, dy, self.post_spec, len(post) - 1, post[-1])
         dz0 = self._torso_bwd("post", self.post_spec, post, dy)
         dhs = b.get("g_dhs", (R, H))

@@ -41,21 +41,7 @@ constexpr float FMIN_ = -3.4028234663852886e38f;
 constexpr int MAXB = 4;          // max blocks
 constexpr int MAXA = 8;          // max agents of the fused path (token staging registers)
 constexpr int QP = 272;          // LDS pitch of a [q|k|v|g] token row: 16 mod 64 -> the (env, kq) float4 pattern is conflict-minimal
-constexpr int UP = 80;
-           // LDS pitch of a 64-wide row
-
-// Timing experiments only (scripts/debug/act_ab.sh; results are WRONG with them): -DMAGPO_ACT_X_NOLOAD replaces every retention-state load
-// by a constant, -DMAGPO_ACT_X_NOSTORE drops the state stores -- what is left is the kernel's compute + scratch-row time.
-#ifdef MAGPO_ACT_X_NOLOAD
-#define XLOAD(p) make_float4(1e-3f, 2e-3f, 3e-3f, 4e-3f)
-#else
-#define XLOAD(p) ld4nt(p)
-#endif
-#ifdef MAGPO_ACT_X_NOSTORE
-#define XSTORE(p, v) do { if ((v).x == 123.456f) st4nt(p, v); } while (0)
-#else
-#define XSTORE(p, v) st4nt(p, v)
-#endif
+constexpr int UP = 80;           // LDS pitch of a 64-wide row
 
 struct ActBlk {
   const float *qkvg_t, *wo_t, *ln1, *ln2, *gn_g, *gn_b;                                     // encoder block
@@ -103,26 +89,23 @@ __device__ unsigned long long g_act_prof[32];
 // ENC: ntok = A, all tokens staged from the global [q|k|v|g] rows `hist`; u rows -> global uout[(env*A + a)*64].
 // DEC: ntok = i + 1, tokens a < i staged from the global k|v history (hist rows, columns hcol..hcol+127), token i read
 //      from the wave's TQ tile; u -> LDS tile U[env].
-// The first state of a pass can be PRIMED: its loads are issued by the caller before the dense phase that precedes the pass
-// (prime_state), so that the memory system also has work while the wave runs MFMA / VALU code (one wave per SIMD: nothing else hides it).
-__device__ __forceinline__ void prime_state(float4 (&dst)[16], const float* __restrict__ Se, int lane) {
-  const int c4 = 4 * (lane & 15), rg = lane >> 4;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) dst[r] = ld4nt(Se + (16 * rg + r) * 64 + c4);
-}
+// The first state of the candidate pass (self_prepass_cand) is PRIMED: its loads are issued by the caller before the dense phase that
+// precedes the pass, so that the memory system also has work while the wave runs MFMA / VALU code (one wave per SIMD: nothing else hides
+// it).  The same for the first state of the ret_pass calls was measured on one box, 16 384 envs: 582 / 584 us with, 574 / 575 us without
+// (4 096 envs: 280 vs 273) -- with 1 024 independent waves the memory system already has work while a wave runs its dense phase; the
+// extra live registers cost more.  Removed.
 __device__ __forceinline__ void prime_state_perm(float4 (&dst)[16], const float* __restrict__ Se, int lane) {   // row order of self_prepass_cand
   const int c4 = 4 * (lane & 15), kq = lane >> 4;
 #pragma unroll
   for (int j = 0; j < 16; ++j) dst[j] = ld4nt(Se + (16 * (j >> 2) + 4 * kq + (j & 3)) * 64 + c4);
 }
 
-template <int MODE, int NA, int NBUF, int NH, bool PRIMED = false>
+template <int MODE, int NA, int NBUF, int NH>
 __device__ __forceinline__ void ret_pass(float* TQ, float* HK, float* U, float* __restrict__ S0 /* head 0 of this block */, long NS,
                                          const ActArgs& a, int env0, int nvalid, int i, const float* __restrict__ hist, long ldh,
                                          int hcol, float* __restrict__ uout, long ldu, const float* __restrict__ gamma,
                                          const float* __restrict__ beta, int write_state, unsigned long long dmask,
-                                         const float* __restrict__ qsrc = nullptr, long ldq = 0, int apply_pending = 0,
-                                         const float4* __restrict__ primed = nullptr) {
+                                         const float* __restrict__ qsrc = nullptr, long ldq = 0, int apply_pending = 0) {
   const int lane = threadIdx.x, c4 = 4 * (lane & 15), rg = lane >> 4;
   const int A = a.A, nh = NH ? NH : a.nh, hs = NH ? AE / NH : a.hs, gs = NH ? AE / (NH * NH) : a.gs;   // NH = 0: run-time head count
   // (the team size as a compile-time constant -- token loops without uniform branches -- was measured in round 4: 484.6 vs 486.6 us, nothing)
@@ -151,14 +134,12 @@ __device__ __forceinline__ void ret_pass(float* TQ, float* HK, float* U, float* 
   float4 buf[NBUF][16], hreg[NBUF][NA];
   RT_DECL();
   const int npairs = nvalid * nh;
-  auto prefetch = [&](float4 (&dst)[16], float4 (&tok)[NA], int pair, bool with_state = true) {
+  auto prefetch = [&](float4 (&dst)[16], float4 (&tok)[NA], int pair) {
     pair = min(pair, npairs - 1);
     const int e = pair / nh, h = pair - e * nh;
     const float* Se = S0 + (long)h * NS + (long)(env0 + e) * 4096;
-    if (with_state) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) dst[r] = XLOAD(Se + (16 * rg + r) * 64 + c4);
-    }
+    for (int r = 0; r < 16; ++r) dst[r] = ld4nt(Se + (16 * rg + r) * 64 + c4);
     const long row0 = (long)(env0 + e) * A;
 #pragma unroll
     for (int t = 0; t < NA; ++t) {
@@ -174,15 +155,7 @@ __device__ __forceinline__ void ret_pass(float* TQ, float* HK, float* U, float* 
     }
   };
 #pragma unroll
-  for (int j = 0; j < NBUF - 1; ++j) {
-    if (PRIMED && j == 0) {   // pair 0's state was requested by the caller (prime_state); only its token rows are loaded here
-#pragma unroll
-      for (int r = 0; r < 16; ++r) buf[0][r] = primed[r];
-      prefetch(buf[0], hreg[0], 0, false);
-    } else {
-      prefetch(buf[j], hreg[j], j);
-    }
-  }
+  for (int j = 0; j < NBUF - 1; ++j) prefetch(buf[j], hreg[j], j);
   for (int base = 0; base < npairs; base += NBUF) {
 #pragma unroll
     for (int j = 0; j < NBUF; ++j) {
@@ -240,7 +213,7 @@ __device__ __forceinline__ void ret_pass(float* TQ, float* HK, float* U, float* 
       }
       if (write_state && live) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) XSTORE(Se + (16 * rg + r) * 64 + c4, s[r]);
+        for (int r = 0; r < 16; ++r) st4nt(Se + (16 * rg + r) * 64 + c4, s[r]);
       }
       if (MODE == 4) {   // the outputs see kappa S
         const float kp = a.kappa[h];
@@ -311,7 +284,7 @@ __device__ __forceinline__ void self_prepass_cand(float* HK, float* PEQ, float* 
     const float* Se = S0 + (long)(env0 + e) * 4096;
     if (with_state) {
 #pragma unroll
-      for (int j = 0; j < 16; ++j) dst[j] = XLOAD(Se + (16 * (j >> 2) + 4 * kq + (j & 3)) * 64 + c4);
+      for (int j = 0; j < 16; ++j) dst[j] = ld4nt(Se + (16 * (j >> 2) + 4 * kq + (j & 3)) * 64 + c4);
     }
     const long row0 = (long)(env0 + e) * A;
 #pragma unroll
@@ -360,7 +333,7 @@ __device__ __forceinline__ void self_prepass_cand(float* HK, float* PEQ, float* 
       if (live) {
         float* Se = S0 + (long)(env0 + e) * 4096;
 #pragma unroll
-        for (int j = 0; j < 16; ++j) XSTORE(Se + (16 * (j >> 2) + 4 * kq + (j & 3)) * 64 + c4, s[j]);
+        for (int j = 0; j < 16; ++j) st4nt(Se + (16 * (j >> 2) + 4 * kq + (j & 3)) * 64 + c4, s[j]);
       }
 #pragma unroll
       for (int j = 0; j < 16; ++j) { s[j].x *= kappa; s[j].y *= kappa; s[j].z *= kappa; s[j].w *= kappa; }
@@ -404,10 +377,7 @@ __device__ __forceinline__ void self_prepass_cand(float* HK, float* PEQ, float* 
 // hist (NA > 4 only): the k | v history rows of this env (token t at hist + t * 256, v at + 64) are then streamed through two row
 // pairs (one in use, one in flight) instead of being held for all NA - 1 earlier agents at once: 14 rows = 224 VGPRs for 8-agent
 // teams, which the register file does not have beside the state buffers (249 values went to scratch).
-#ifndef MAGPO_ACT_STREAM4
-#define MAGPO_ACT_STREAM4 0   // 1: the k | v history rows of the earlier agents are streamed for teams of <= 4 agents too (register relief)
-#endif
-template <int NH, int NA, bool STREAM = (NA > 4 || MAGPO_ACT_STREAM4)>
+template <int NH, int NA, bool STREAM = (NA > 4)>
 __device__ __forceinline__ Row cross_ret(const ActArgs& a, const Row& q, const Row& kc, const Row& vc, const Row& gc, const Row& p2,
                                          const Row (&hk)[NA - 1], const Row (&hv)[NA - 1], int i, const float* __restrict__ gamma,
                                          const float* __restrict__ beta, int kq, const float* __restrict__ hist = nullptr) {
@@ -486,48 +456,18 @@ __device__ __forceinline__ Row cross_ret(const ActArgs& a, const Row& q, const R
 #define PROF(k)
 #endif
 
-// State buffers per wave at 16 envs per wave (the -D hook exists for scripts/debug/act_nbuf.sh).  Measured on MI355X, us per launch for
-// 2 / 3 / 4 buffers: 698 / 769 / 815 (A = 4, one block, 16 384 envs), 2340 / 2863 / 4893 (A = 8, two blocks): the third buffer costs 80
-// VGPRs, which pushes 94 values into scratch, and every scratch reload waits with vmcnt(0), i.e. drains the very prefetches the buffer
-// was meant to keep in flight.
-#ifndef MAGPO_ACT_NBUF16
-#define MAGPO_ACT_NBUF16 2
-#endif
-// A/B hook (scripts/debug/act_ab.sh): 1 = the first state of a pass is requested ahead of the dense phase in front of it instead of at the
-// start of the pass.  Measured on one box, 16 384 envs: 582 / 584 us with, 574 / 575 us without (4 096 envs: 280 vs 273) -- with 1 024
-// independent waves the memory system already has work while a wave runs its dense phase; the extra live registers cost more.  Off.
-#ifndef MAGPO_ACT_PRIME
-#define MAGPO_ACT_PRIME 0
-#endif
-constexpr int ACT_NBUF16 = MAGPO_ACT_NBUF16;
-#ifndef MAGPO_ACT_NBUF_ENC
-#define MAGPO_ACT_NBUF_ENC MAGPO_ACT_NBUF16
-#endif
-#ifndef MAGPO_ACT_NBUF_PRE
-#define MAGPO_ACT_NBUF_PRE MAGPO_ACT_NBUF16
-#endif
-#ifndef MAGPO_ACT_NBUF_CAND
-#define MAGPO_ACT_NBUF_CAND 2
-#endif
-
-#ifndef MAGPO_ACT_DEFER
-#define MAGPO_ACT_DEFER 1   // 1: the non-EARLY waves run the candidate pre-pass of the next step at the end of the launch (see defer_wave)
-#endif
-#ifndef MAGPO_ACT_STAGGER_MOD
-#define MAGPO_ACT_STAGGER_MOD 2
-#define MAGPO_ACT_STAGGER_EARLY 1
-#endif
-#ifndef MAGPO_ACT_STAGGER_SHIFT
-#define MAGPO_ACT_STAGGER_SHIFT 3   // workgroups alternate between the two phase orders in groups of 2^shift
-#endif
-#ifndef MAGPO_ACT_STAGGER
-#define MAGPO_ACT_STAGGER 1   // 1: the workgroups alternate between two phase orders (see stag / defer_wave in k_sable_act)
-#endif
-#ifndef MAGPO_ACT_WPE
-#define MAGPO_ACT_WPE 1   // waves per SIMD the register allocation aims at (A/B hook)
-#endif
+// State buffers per wave at 16 envs per wave.  Measured on MI355X, us per launch for 2 / 3 / 4 buffers: 698 / 769 / 815 (A = 4, one block,
+// 16 384 envs), 2340 / 2863 / 4893 (A = 8, two blocks): the third buffer costs 80 VGPRs, which pushes 94 values into scratch, and every
+// scratch reload waits with vmcnt(0), i.e. drains the very prefetches the buffer was meant to keep in flight.
+constexpr int ACT_NBUF16 = 2;
+constexpr int ACT_NBUF_CAND = 2;       // state buffers of the candidate pass (self_prepass_cand), every wave shape
+// The workgroups alternate between two phase orders (see stag / defer_wave in k_sable_act) in groups of 2^SHIFT: of every MOD groups the
+// first EARLY run the candidate pre-pass ahead of the encoder, the others run it at the end of the launch for the next step (DEFER).
+constexpr int ACT_STAGGER_SHIFT = 3, ACT_STAGGER_MOD = 2, ACT_STAGGER_EARLY = 1;
+constexpr bool ACT_DEFER = true;
+constexpr int ACT_WPE = 1;             // waves per SIMD the register allocation aims at
 template <int EPW, int NA, int NH>
-__global__ __launch_bounds__(64, MAGPO_ACT_WPE) void k_sable_act(ActArgs a) {
+__global__ __launch_bounds__(64, ACT_WPE) void k_sable_act(ActArgs a) {
   extern __shared__ __align__(16) float smem[];
   float* TQ = smem;                  // [EPW][QP]  this iteration's [q|k|v|g] rows, one per env
   float* HK = TQ + EPW * QP;         // [A][QP]    staged token rows of the env being processed
@@ -537,6 +477,7 @@ __global__ __launch_bounds__(64, MAGPO_ACT_WPE) void k_sable_act(ActArgs a) {
 #ifdef MAGPO_ACT_PROF
   unsigned long long t_last = wall_clock64();
 #endif
+  constexpr int NBF = EPW == 16 ? ACT_NBUF16 : 2;   // state buffers of the ret_pass calls
   const int lane = threadIdx.x, env = lane & 15, kq = lane >> 4, m = env;
   const int env0 = blockIdx.x * EPW;
   const int nvalid = min(EPW, a.N - env0);
@@ -551,10 +492,6 @@ __global__ __launch_bounds__(64, MAGPO_ACT_WPE) void k_sable_act(ActArgs a) {
   // envs whose episode ended on the previous step (bit e): one flag load per kernel, kept out of the retention pipeline
   const unsigned long long dmask = a.done ? __ballot(valid && kq == 0 && a.done[ge] != 0) : 0ull;
 
-  // first state of the block-0 encoder pass: in flight while the token rows are computed
-  float4 pS[16];
-  if (MAGPO_ACT_PRIME) prime_state(pS, a.S_enc + (long)env0 * 4096, lane);
-
   // candidate path of the block-0 self-retention: one head (the state tile is the whole 64 x 64 matrix)
   const bool cand = nh_ == 1;
   // The candidate pre-pass (block-0 self-retention states: a third of the launch's state traffic) depends on the previous launch's pending
@@ -565,8 +502,8 @@ __global__ __launch_bounds__(64, MAGPO_ACT_WPE) void k_sable_act(ActArgs a) {
   //   DEFERRING waves run it LAST, for the NEXT step (a.defer): after the decoder the step's k | v rows are known, the next step count is
   //     this one + 1 unless the episode ends, and an ended episode means a zero state and a zero table -- fixed up by the next launch
   //     (a.precand) from its `done` flags.  They stream states while the EARLY waves decode, and decode while those stream.
-  const bool stag = MAGPO_ACT_STAGGER && (int)((blockIdx.x >> MAGPO_ACT_STAGGER_SHIFT) % MAGPO_ACT_STAGGER_MOD) < MAGPO_ACT_STAGGER_EARLY;
-  const bool defer_wave = cand && MAGPO_ACT_DEFER && MAGPO_ACT_STAGGER && !stag;
+  const bool stag = (int)((blockIdx.x >> ACT_STAGGER_SHIFT) % ACT_STAGGER_MOD) < ACT_STAGGER_EARLY;
+  const bool defer_wave = cand && ACT_DEFER && !stag;
   // (a third role -- the pre-pass between the cross-state pre-pass and the decoder for every third group -- was measured: 498 vs 499 us)
   auto cand_pass = [&](const Row& pe_q, unsigned long long dm, bool apply) __attribute__((always_inline)) {
     const ActBlk& B = a.blk[0];
@@ -587,7 +524,7 @@ __global__ __launch_bounds__(64, MAGPO_ACT_WPE) void k_sable_act(ActArgs a) {
       lsync();                                                                                                               \
       Row xq[MT_];                                                                                                           \
       _Pragma("unroll") for (int mt = 0; mt < MT_; ++mt) xq[mt] = xout_[mt];                                                 \
-      self_prepass_cand<NA, MT_, (EPW == 16 ? MAGPO_ACT_NBUF_CAND : 2)>(HK, PEQ, a.S_d1, a, env0, nvalid, B.qkvg1, xq, dm, pS1, apply);              \
+      self_prepass_cand<NA, MT_, ACT_NBUF_CAND>(HK, PEQ, a.S_d1, a, env0, nvalid, B.qkvg1, xq, dm, pS1, apply);                            \
     }
     if (ntile == 1) CAND_ROWS(1) else if (ntile == 2) CAND_ROWS(2) else CAND_ROWS(3)
 #undef CAND_ROWS
@@ -661,10 +598,10 @@ __global__ __launch_bounds__(64, MAGPO_ACT_WPE) void k_sable_act(ActArgs a) {
     }
     wsync();
     PROF(0);
-    if (b == 0) ret_pass<0, NA, (EPW == 16 ? MAGPO_ACT_NBUF_ENC : 2), NH, MAGPO_ACT_PRIME != 0>(TQ, HK, U, a.S_enc, NS, a, env0, nvalid, 0, a.qkvg, 256, 0, a.u, AE, B.gn_g, B.gn_b, a.value_only ? 0 : 1, dmask, nullptr, 0, 0, pS);
-    else ret_pass<0, NA, (EPW == 16 ? ACT_NBUF16 : 2), NH>(TQ, HK, U, a.S_enc + (long)b * nh_ * NS, NS, a, env0, nvalid, 0, a.qkvg, 256, 0, a.u, AE, B.gn_g, B.gn_b, a.value_only ? 0 : 1, dmask);
-    // the first cross-retention state of the decoder pre-pass rides along with the encoder's post-retention dense phase
-    if (MAGPO_ACT_PRIME && b == nb - 1 && !a.value_only) prime_state(pS, a.S_d2 + (long)env0 * 4096, lane);
+    // (block 0 and the later blocks are two inlined copies of one instantiation: a single call site makes the kernel 10 - 13 % shorter, which is
+    // a change of the compiled kernel that has not been measured)
+    if (b == 0) ret_pass<0, NA, NBF, NH>(TQ, HK, U, a.S_enc, NS, a, env0, nvalid, 0, a.qkvg, 256, 0, a.u, AE, B.gn_g, B.gn_b, a.value_only ? 0 : 1, dmask);
+    else ret_pass<0, NA, NBF, NH>(TQ, HK, U, a.S_enc + (long)b * nh_ * NS, NS, a, env0, nvalid, 0, a.qkvg, 256, 0, a.u, AE, B.gn_g, B.gn_b, a.value_only ? 0 : 1, dmask);
     wsync();
     PROF(1);
     for (int t0 = 0; t0 < A; t0 += 4) {
@@ -714,7 +651,6 @@ __global__ __launch_bounds__(64, MAGPO_ACT_WPE) void k_sable_act(ActArgs a) {
     PROF(2);
   }
   PROF(3);
-  constexpr int NBF = EPW == 16 ? ACT_NBUF16 : 2;
   // flush: S <- kappa S + sum_a k_a^T v_a with the rows in the scratch (this launch's, or the pending ones of the previous launch)
   auto flush_states = [&](bool d1_block0_done) {
     wsync();
@@ -734,8 +670,8 @@ __global__ __launch_bounds__(64, MAGPO_ACT_WPE) void k_sable_act(ActArgs a) {
   // zeroing), written back, and gives from registers what the decoder needs from kappa S
   for (int b = 0; b < nb; ++b) {
     const ActBlk& B = a.blk[b];
-    if (b == 0) ret_pass<4, NA, (EPW == 16 ? MAGPO_ACT_NBUF_PRE : 2), NH, MAGPO_ACT_PRIME != 0>(TQ, HK, U, a.S_d2, NS, a, env0, nvalid, 0, B.kvg2, 256, 0, B.kvg2 + 192, 256, B.gn2_g, B.gn2_b, 1, dmask,
-                                               B.q2, AE, a.pending, pS);
+    if (b == 0) ret_pass<4, NA, NBF, NH>(TQ, HK, U, a.S_d2, NS, a, env0, nvalid, 0, B.kvg2, 256, 0, B.kvg2 + 192, 256, B.gn2_g, B.gn2_b, 1, dmask,
+                                         B.q2, AE, a.pending);   // (two copies, as in the encoder)
     else ret_pass<4, NA, NBF, NH>(TQ, HK, U, a.S_d2 + (long)b * nh_ * NS, NS, a, env0, nvalid, 0, B.kvg2, 256, 0, B.kvg2 + 192, 256, B.gn2_g, B.gn2_b, 1, dmask,
                                   B.q2, AE, a.pending);
     PROF(19);
@@ -820,7 +756,7 @@ __global__ __launch_bounds__(64, MAGPO_ACT_WPE) void k_sable_act(ActArgs a) {
         Row hk2[NA - 1], hv2[NA - 1];
 #pragma unroll
         for (int t = 0; t < NA - 1; ++t) {
-          if (NA <= 4 && !MAGPO_ACT_STREAM4 && t < i) { hk2[t] = row_load(B.kvg2 + (ge * A + t) * 256, kq); hv2[t] = row_load(B.kvg2 + (ge * A + t) * 256 + 64, kq); }
+          if (NA <= 4 && t < i) { hk2[t] = row_load(B.kvg2 + (ge * A + t) * 256, kq); hv2[t] = row_load(B.kvg2 + (ge * A + t) * 256 + 64, kq); }
         }
         const Row p2 = row_load(B.kvg2 + row * 256 + 192, kq);
         const Row q2 = row_load(B.q2 + row * AE, kq);
@@ -883,11 +819,7 @@ __global__ __launch_bounds__(64, MAGPO_ACT_WPE) void k_sable_act(ActArgs a) {
         const uint32_t bits = random_bits32(k0, k1, (uint32_t)(ge * a.K + n));
         const float f = __uint_as_float((bits >> 9) | 0x3f800000u) - 1.0f;
         const float uu = fmaxf(1.17549435e-38f, f + 1.17549435e-38f);
-#ifdef MAGPO_X_FASTGUMBEL   // timing experiment: hardware fp32 logs (NOT the oracle's correctly rounded value)
-        const float gmb = -__logf(-__logf(uu));
-#else
         const float gmb = (float)(-log(-log((double)uu)));
-#endif
         const float vv = gmb + lp;
         if (vv > best || (vv == best && n < arg)) { best = vv; arg = n; best_lp = lp; }
       }

@@ -92,12 +92,7 @@ __device__ __forceinline__ Row row_add(const Row& a, const Row& b) {
   for (int j = 0; j < 16; ++j) r.v[j] = a.v[j] + b.v[j];
   return r;
 }
-// Timing experiments only (results are WRONG with them; scripts/debug/act_ab2.sh): -DMAGPO_X_NOROWMATH makes RMSNorm / GELU pass-through,
-// -DMAGPO_X_NOW replaces the weight-fragment loads of the dense layers by constants, -DMAGPO_X_NOMFMA drops their MFMAs.
 __device__ __forceinline__ Row row_rms(const Row& x, const float* scale, int kq) {
-#ifdef MAGPO_X_NOROWMATH
-  return x;
-#endif
   Row q;
 #pragma unroll
   for (int j = 0; j < 16; ++j) q.v[j] = x.v[j] * x.v[j];
@@ -111,9 +106,6 @@ __device__ __forceinline__ Row row_rms(const Row& x, const float* scale, int kq)
 // GELU (tanh form) on the hardware exp / rcp units: the fused kernels run one or two waves per SIMD and are VALU-issue bound,
 // libm's tanhf is ~40 instructions per element (abs. error of the fast form ~1e-7, far inside the fp32 parity tolerance)
 __device__ __forceinline__ Row row_gelu(const Row& x) {
-#ifdef MAGPO_X_NOROWMATH
-  return x;
-#endif
   Row r;
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
@@ -124,16 +116,6 @@ __device__ __forceinline__ Row row_gelu(const Row& x) {
 }
 
 // ---- dense layer, transposed on 16x16x4 fp32 MFMA: out(g, acc) receives features 16 g + 4 kq + (0..3) of every env ------
-#ifdef MAGPO_X_NOW
-#define WLD(p) make_float4(1e-3f, -2e-3f, 3e-3f, -1e-3f)
-#else
-#define WLD(p) ld4g(p)
-#endif
-#ifdef MAGPO_X_NOMFMA
-#define WMFMA(a, b, c) f32x4{c[0] + (a) * (b), c[1], c[2], c[3]}
-#else
-#define WMFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0)
-#endif
 // Weight operand layouts: the transposed copy Wt [n][64] of magpo_transpose_pad (FRAG = false: lane (m, kq) reads 16 bytes of row 16 g + m,
 // i.e. one instruction touches 16 rows x 64 B), or the FRAGMENT-MAJOR copy of the acting kernel (FRAG = true, SableGuider.build_act_weights):
 //   Wf[g][gk][lane = m + 16 kq][4] = Wt[16 g + m][16 gk + 4 kq .. + 3]
@@ -141,19 +123,17 @@ __device__ __forceinline__ Row row_gelu(const Row& x) {
 // its weights from L2 for every token (the acting kernel: 1.15 MB per wave and launch) is bound by those requests, not by the MFMAs.
 template <bool FRAG>
 __device__ __forceinline__ float4 wfrag(const float* __restrict__ Wt, int g, int gk, int m, int kq) {
-  if (FRAG) return WLD(Wt + g * 1024 + gk * 256 + 4 * (m + 16 * kq));
-  return WLD(Wt + (long)(16 * g + m) * AE + 16 * gk + 4 * kq);
+  if (FRAG) return ld4g(Wt + g * 1024 + gk * 256 + 4 * (m + 16 * kq));
+  return ld4g(Wt + (long)(16 * g + m) * AE + 16 * gk + 4 * kq);
 }
-#ifndef MAGPO_WGEMM_PD
-#define MAGPO_WGEMM_PD 4
-#endif
 // The first fragments of a layer can be requested AHEAD of the code that produces the layer's input (wload<NG>() before the row math of the
 // previous layer, wgemm_pre<NG>() after it): a wave that runs alone on its SIMD otherwise sits out one L2 round trip at the top of every
 // dense layer -- ~45 of them per acting step.
-struct WPre { float4 w[MAGPO_WGEMM_PD][4]; };
+constexpr int WGEMM_PD = 4;   // column groups of weight fragments in flight ahead of the MFMAs
+struct WPre { float4 w[WGEMM_PD][4]; };
 template <int NG, bool FRAG>
 __device__ __forceinline__ WPre wload(const float* __restrict__ Wt, int m, int kq) {
-  constexpr int PD = NG < MAGPO_WGEMM_PD ? NG : MAGPO_WGEMM_PD;
+  constexpr int PD = NG < WGEMM_PD ? NG : WGEMM_PD;
   WPre r;
 #pragma unroll
   for (int p = 0; p < PD; ++p)
@@ -163,7 +143,7 @@ __device__ __forceinline__ WPre wload(const float* __restrict__ Wt, int m, int k
 }
 template <int NG, bool FRAG = false, class OUT = void>
 __device__ __forceinline__ void wgemm_pre(const Row& x, const float* __restrict__ Wt, const WPre& pre, int m, int kq, OUT&& out) {
-  constexpr int PD = NG < MAGPO_WGEMM_PD ? NG : MAGPO_WGEMM_PD;   // weight fragments in flight ahead of the MFMAs (column groups)
+  constexpr int PD = NG < WGEMM_PD ? NG : WGEMM_PD;   // weight fragments in flight ahead of the MFMAs (column groups)
   float4 w[PD][4];
 #pragma unroll
   for (int p = 0; p < PD; ++p)
@@ -174,10 +154,10 @@ __device__ __forceinline__ void wgemm_pre(const Row& x, const float* __restrict_
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int gk = 0; gk < 4; ++gk) {
-      acc = WMFMA(w[g % PD][gk].x, x.v[4 * gk], acc);
-      acc = WMFMA(w[g % PD][gk].y, x.v[4 * gk + 1], acc);
-      acc = WMFMA(w[g % PD][gk].z, x.v[4 * gk + 2], acc);
-      acc = WMFMA(w[g % PD][gk].w, x.v[4 * gk + 3], acc);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[g % PD][gk].x, x.v[4 * gk], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[g % PD][gk].y, x.v[4 * gk + 1], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[g % PD][gk].z, x.v[4 * gk + 2], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[g % PD][gk].w, x.v[4 * gk + 3], acc, 0, 0, 0);
     }
     if (g + PD < NG) {
 #pragma unroll
@@ -210,10 +190,10 @@ __device__ __forceinline__ void wgemm_multi(const Row (&x)[NT], int nt, const fl
       if (t < nt) {
 #pragma unroll
         for (int gk = 0; gk < 4; ++gk) {
-          acc[t] = WMFMA(w[g % PD][gk].x, x[t].v[4 * gk], acc[t]);
-          acc[t] = WMFMA(w[g % PD][gk].y, x[t].v[4 * gk + 1], acc[t]);
-          acc[t] = WMFMA(w[g % PD][gk].z, x[t].v[4 * gk + 2], acc[t]);
-          acc[t] = WMFMA(w[g % PD][gk].w, x[t].v[4 * gk + 3], acc[t]);
+          acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[g % PD][gk].x, x[t].v[4 * gk], acc[t], 0, 0, 0);
+          acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[g % PD][gk].y, x[t].v[4 * gk + 1], acc[t], 0, 0, 0);
+          acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[g % PD][gk].z, x[t].v[4 * gk + 2], acc[t], 0, 0, 0);
+          acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[g % PD][gk].w, x[t].v[4 * gk + 3], acc[t], 0, 0, 0);
         }
       }
     }

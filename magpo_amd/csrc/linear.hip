@@ -1,15 +1,16 @@
 // Row-batched dense layers on fp32 MFMA (v_mfma_f32_32x32x2_f32) for gfx950.
 //
-//   k_linear<KIN> : Y[R,NOUT] = act(X[R,KIN] @ W + b), W given transposed ("Wt[NOUT_pad][KIN]").
+//   k_linear_lds<KIN, NW> : Y[R,NOUT] = act(X[R,KIN] @ W + b), W given transposed ("Wt[NOUT_pad][KIN]").
 //                   The same kernel computes dX = dY @ W^T by passing W in its natural [in][out]
 //                   layout as "Wt" (replaces XLA's dot_general for flax nn.Dense and the Sable
 //                   projections: sable_network.py:93-109,258-284, retention.py:73-75,294, base.py:175-181).
 //   k_wgrad<NB>   : dW[KIN,NOUT] partial sums = X^T dY per workgroup slab (+ column sums of dY for
 //                   the bias), reduced in fixed order by k_reduce_slabs (bit-stable reruns).
 //
-// Tile: 64 rows per workgroup (4 waves as 2x2 quadrants of 32x32 accumulators).  X rows are staged
-// once in LDS ([64][KIN+4] floats, ds_read_b128 per lane conflict-free); B fragments come
-// straight from L2 into VGPRs (each lane owns one output column and 32 contiguous k's).
+// Tile of k_linear_lds: 32 rows x (32 NW) columns per workgroup, one 32x32 accumulator per wave.  A wave keeps the weight
+// fragments of its 32 columns in VGPRs (each lane owns one output column and half of its k's) for the whole persistent loop;
+// the X rows go through a double-buffered LDS tile ([32][KIN+4] floats, ds_read_b128 per lane conflict-free) that the next
+// tile's coalesced loads refill while this tile's MFMAs run.  See the comment at the kernel.
 #include "common.hpp"
 #include <stdlib.h>
 
@@ -17,160 +18,6 @@ namespace magpo {
 
 // MASKPOS: y = aux > 0 ? y : 0 (ReLU backward fused into dX = dY W^T); TANHBWD: y *= 1 - aux^2 (tanh backward, aux = the forward's output)
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_SWISH = 3, ACT_MASKPOS = 4, ACT_TANH = 5, ACT_TANHBWD = 6 };
-
-template <int KIN>
-__global__ __launch_bounds__(256) void k_linear(const float* __restrict__ X, int ldx,
-                                                const float* __restrict__ Wt, const float* __restrict__ bias,
-                                                float* __restrict__ Y, int ldy, float* __restrict__ Ypre,
-                                                int R, int NOUT, int act) {
-  constexpr int LD = KIN + LDP;
-  extern __shared__ __align__(16) float xs[];  // [64][LD]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1, lr = lane & 31, h = lane >> 5;
-  const long row0 = (long)blockIdx.x * 64;
-
-  // stage X tile
-  constexpr int F4 = KIN / 4;
-  for (int i = tid; i < 64 * F4; i += 256) {
-    int r = i / F4, c4 = i - r * F4;
-    long gr = row0 + r;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (gr < R) v = *reinterpret_cast<const float4*>(X + gr * (long)ldx + 4 * c4);
-    *reinterpret_cast<float4*>(&xs[r * LD + 4 * c4]) = v;
-  }
-  __syncthreads();
-
-  const float* arow = &xs[(32 * wr + lr) * LD + 32 * h];
-  const int nblk = (NOUT + 63) >> 6;
-  for (int nb = 0; nb < nblk; ++nb) {
-    const int n = nb * 64 + 32 * wc + lr;
-    if (nb * 64 + 32 * wc >= NOUT) continue;  // wave-uniform
-    f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    const float* wrow = Wt + (long)n * KIN + 32 * h;  // Wt is padded to a multiple of 32 rows
-#pragma unroll 1
-    for (int kc = 0; kc < KIN / 64; ++kc) {
-      float4 b[8], a[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) b[u] = *reinterpret_cast<const float4*>(wrow + kc * 64 + 4 * u);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) a[u] = *reinterpret_cast<const float4*>(arow + kc * 64 + 4 * u);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u].x, b[u].x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u].y, b[u].y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u].z, b[u].z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u].w, b[u].w, acc, 0, 0, 0);
-      }
-    }
-    if (n < NOUT) {
-      const float bv = bias ? bias[n] : 0.f;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        long gr = row0 + 32 * wr + (i & 3) + 8 * (i >> 2) + 4 * h;
-        if (gr < R) {
-          float v = acc[i] + bv;
-          if (Ypre) Ypre[gr * (long)ldy + n] = v;
-          if (act == ACT_RELU) v = fmaxf(v, 0.f);
-          else if (act == ACT_GELU) v = gelu_tanh(v);
-          else if (act == ACT_SWISH) v = swishf_(v);
-          else if (act == ACT_TANH) v = tanhf(v);
-          Y[gr * (long)ldy + n] = v;
-        }
-      }
-    }
-  }
-}
-
-// Wave-autonomous form for KIN in {64, 128} when a pre-activation copy is requested: every wave owns 32*NCB output columns, keeps their weight
-// fragments in VGPRs for the whole persistent loop and streams 32-row activation tiles straight from HBM
-// (each lane reads one contiguous half-row, a wave one contiguous 32 x KIN block).  No LDS, no barriers:
-// latency is hidden by several independent waves per SIMD.
-template <int KIN, int NCB>
-__global__ __launch_bounds__(256) void k_linear_w(const float* __restrict__ X, int ldx, const float* __restrict__ Wt,
-                                                  const float* __restrict__ bias, float* __restrict__ Y, int ldy,
-                                                  float* __restrict__ Ypre, int R, int NOUT, int act) {
-  constexpr int KH = KIN / 2;  // k values per lane half
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 31, h = lane >> 5;
-  const int c0 = (blockIdx.y * (blockDim.x >> 6) + wave) * 32 * NCB;
-  if (c0 >= NOUT) return;
-  float4 wf[NCB][KH / 4];
-  float bv[NCB];
-#pragma unroll
-  for (int b = 0; b < NCB; ++b) {
-    const int n = c0 + 32 * b + lr;
-    const bool on = c0 + 32 * b < NOUT;  // Wt rows are padded to a multiple of 32
-    bv[b] = (bias && n < NOUT) ? bias[n] : 0.f;
-#pragma unroll
-    for (int u = 0; u < KH / 4; ++u)
-      wf[b][u] = on ? *reinterpret_cast<const float4*>(Wt + (long)n * KIN + h * KH + 4 * u) : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  const int ntiles = (R + 31) >> 5;
-  float4 af[KH / 4], an[KH / 4];
-  auto fetch = [&](int tile, float4* dst) {
-    // unconditional loads from a clamped row (rows past the end are never stored): no exec-masked block in the pipeline
-    const long row = min((long)tile * 32 + lr, (long)R - 1);
-    const float* xp = X + row * (long)ldx + h * KH;
-#pragma unroll
-    for (int u = 0; u < KH / 4; ++u) dst[u] = *reinterpret_cast<const float4*>(xp + 4 * u);
-  };
-  fetch(blockIdx.x, af);
-  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    fetch(tile + gridDim.x, an);  // next tile's activations are in flight while this tile's MFMAs run
-    f32x16 acc[NCB];
-#pragma unroll
-    for (int b = 0; b < NCB; ++b)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[b][i] = 0.f;
-#pragma unroll
-    for (int u = 0; u < KH / 4; ++u) {
-#pragma unroll
-      for (int b = 0; b < NCB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[u].x, wf[b][u].x, acc[b], 0, 0, 0);
-#pragma unroll
-      for (int b = 0; b < NCB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[u].y, wf[b][u].y, acc[b], 0, 0, 0);
-#pragma unroll
-      for (int b = 0; b < NCB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[u].z, wf[b][u].z, acc[b], 0, 0, 0);
-#pragma unroll
-      for (int b = 0; b < NCB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[u].w, wf[b][u].w, acc[b], 0, 0, 0);
-    }
-    if (!Ypre && act <= ACT_RELU && (long)tile * 32 + 32 <= R && c0 + 32 * NCB <= NOUT) {
-      // the common case (whole tile, plain / relu output): straight-line stores, no per-element exec masking
-#pragma unroll
-      for (int b = 0; b < NCB; ++b) {
-        float* yp = Y + ((long)tile * 32 + 4 * h) * (long)ldy + c0 + 32 * b + lr;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          float v = acc[b][i] + bv[b];
-          if (act == ACT_RELU) v = fmaxf(v, 0.f);
-          yp[(long)((i & 3) + 8 * (i >> 2)) * ldy] = v;
-        }
-      }
-    } else {
-#pragma unroll
-      for (int b = 0; b < NCB; ++b) {
-        const int n = c0 + 32 * b + lr;
-        if (n < NOUT) {
-#pragma unroll
-          for (int i = 0; i < 16; ++i) {
-            const long gr = (long)tile * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-            if (gr < R) {
-              float v = acc[b][i] + bv[b];
-              if (Ypre) Ypre[gr * (long)ldy + n] = v;
-              if (act == ACT_RELU) v = fmaxf(v, 0.f);
-              else if (act == ACT_GELU) v = gelu_tanh(v);
-              else if (act == ACT_SWISH) v = swishf_(v);
-              else if (act == ACT_TANH) v = tanhf(v);
-              Y[gr * (long)ldy + n] = v;
-            }
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < KH / 4; ++u) af[u] = an[u];
-  }
-}
 
 // ---------------------------------------------------------------------------------------------------
 // Prologue-fused skinny GEMM for acting (64 -> NOUT): the row-wise op that precedes a dense layer in the
@@ -335,7 +182,7 @@ __global__ __launch_bounds__(256) void k_linear_pro(ProArgs p, const float* __re
   }
 }
 
-// Shared-tile dense layer (every KIN in {64, ..., 384} when no pre-activation copy is requested): a wave owns 32 output columns and
+// Shared-tile dense layer (every KIN in {64, 128, 192, 256, 384}): a wave owns 32 output columns and
 // keeps ALL their weight fragments in VGPRs (KIN/2 registers); the 32-row activation tile is fetched ONCE per workgroup with fully
 // coalesced loads and shared by the waves through a double-buffered LDS tile.  A wave-autonomous form, in which every wave fetched
 // its own copy of the tile as per-lane 128-B row pieces (64 cache lines touched by each load instruction, 4096 line requests per
@@ -1176,69 +1023,41 @@ static auto with_lds(size_t lds) {
   return K;
 }
 
-extern "C" int magpo_linear(const float* X, int ldx, const float* Wt, const float* bias, float* Y, int ldy, float* Ypre,
+extern "C" int magpo_linear(const float* X, int ldx, const float* Wt, const float* bias, float* Y, int ldy, float* mask,
                             long R, int KIN, int NOUT, int act, int variant, hipStream_t stream) {
   if (R <= 0) return MAGPO_OK;
-  if ((ldx & 3) || KIN % 64 || NOUT <= 0) { set_error("magpo_linear: KIN must be a multiple of 64, ldx of 4"); return MAGPO_EINVAL; }
+  if ((ldx & 3) || NOUT <= 0) { set_error("magpo_linear: ldx must be a multiple of 4, NOUT positive"); return MAGPO_EINVAL; }
+  if (KIN != 64 && KIN != 128 && KIN != 192 && KIN != 256 && KIN != 384) { set_error("magpo_linear: KIN must be in {64, 128, 192, 256, 384}"); return MAGPO_EINVAL; }
   // variant 4 = bf16 triples (k_linear_lds<KIN, 4, true>: KIN 128 / 192 with four-wave column blocks; ignored elsewhere)
   if (variant != 0 && variant != 4) { set_error("magpo_linear: variant must be 0 or 4"); return MAGPO_EINVAL; }
-  const float* aux = nullptr;
   if (act < ACT_NONE || act > ACT_TANHBWD) { set_error("magpo_linear: act must be in [0, 6]"); return MAGPO_EINVAL; }
-  if (act == ACT_MASKPOS || act == ACT_TANHBWD) {   // the Ypre argument carries the mask INPUT (same shape / stride as Y), nothing else is written
-    if (!Ypre) { set_error("magpo_linear: act 4 / 6 (backward masks) need the mask tensor in the Ypre argument"); return MAGPO_EINVAL; }
-    aux = Ypre;
-    Ypre = nullptr;
-  }
-  const bool shared_tile = KIN == 64 || KIN == 128 || KIN == 192 || KIN == 256 || KIN == 384;
-  if (act == ACT_TANHBWD && !shared_tile) { set_error("magpo_linear: act 6 needs KIN in {64, 128, 192, 256, 384}"); return MAGPO_EINVAL; }
-  if (shared_tile && !Ypre) {
-    // shared-tile form: 4 waves per block, 2 when the column groups do not fill blocks of 4 (every wave then has MFMA work);
-    // column groups past NOUT idle in the MFMA part but help loading
-    const int ncg = (NOUT + 31) / 32;
-    const int nw = (ncg % 4 == 0) ? 4 : 2;
-    const int gy = (ncg + nw - 1) / nw;
-    const long ntiles = (R + 31) / 32;
-    long wk2 = 2048 / nw;   // about 2 waves per SIMD; LDS 2 x 32 x (KIN + 4) floats per block
-    // several column blocks per row walker: all of them co-resident (walkers x column blocks <= resident workgroups), so the
-    // column blocks of a walker -- same XCD, since the walker count is a multiple of 8 -- read a tile at about the same
-    // time and the re-reads hit that XCD's L2 instead of HBM (in a second round they would come from HBM again)
-    if (gy >= 3) wk2 /= 2;
-    if (wk2 > ntiles) wk2 = ntiles;
-    // (two-wave blocks -- narrow outputs -- are slower on bf16 triples: 128 -> 20 0.86 vs 1.35 ms)
-    const bool bf3 = variant == 4 && (KIN == 128 || KIN == 192) && nw == 4;
-    const size_t lds = bf3 ? (size_t)2 * 3 * 32 * (KIN + 8) * sizeof(__bf16) : (size_t)2 * 32 * (KIN + LDP) * sizeof(float);
-    decltype(&k_linear_lds<64, 4>) k;
-    if (bf3) k = KIN == 128 ? with_lds<k_linear_lds<128, 4, true>>(lds) : with_lds<k_linear_lds<192, 4, true>>(lds);
-    else if (KIN == 64) k = nw == 4 ? with_lds<k_linear_lds<64, 4>>(lds) : with_lds<k_linear_lds<64, 2>>(lds);
-    else if (KIN == 128) k = nw == 4 ? with_lds<k_linear_lds<128, 4>>(lds) : with_lds<k_linear_lds<128, 2>>(lds);
-    else if (KIN == 192) k = nw == 4 ? with_lds<k_linear_lds<192, 4>>(lds) : with_lds<k_linear_lds<192, 2>>(lds);
-    else if (KIN == 256) k = nw == 4 ? with_lds<k_linear_lds<256, 4>>(lds) : with_lds<k_linear_lds<256, 2>>(lds);
-    else k = nw == 4 ? with_lds<k_linear_lds<384, 4>>(lds) : with_lds<k_linear_lds<384, 2>>(lds);
-    hipLaunchKernelGGL(k, dim3((unsigned)wk2, (unsigned)gy), dim3(64 * nw), lds, stream, X, ldx, Wt, bias, Y, ldy, (int)R, NOUT, act, aux);
-    return check_launch("magpo_linear");
-  }
-  // a pre-activation copy is requested
-  if (KIN == 64 || KIN == 128) {
-    // wave-autonomous path: 64 columns per wave, up to 4 waves (256 columns) per workgroup
-    const int cpw = KIN == 64 ? 64 : 32;  // columns per wave (128 per wave was measured slower: 256 VGPRs + spills)
-    const int ncg = (NOUT + cpw - 1) / cpw;
-    const int wpb = (ncg % 4 == 0) ? 4 : ((ncg % 2 == 0) ? 2 : 1);
-    const long ntiles = (R + 31) / 32;
-    long walkers = 2048 / ncg;  // about one resident wave set (2 waves per SIMD on 256 CUs, register-limited)
-    if (walkers < 1) walkers = 1;
-    if (walkers > ntiles) walkers = ntiles;
-    dim3 grid((unsigned)walkers, (unsigned)(ncg / wpb)), block(64 * wpb);
-    if (KIN == 64) hipLaunchKernelGGL((k_linear_w<64, 2>), grid, block, 0, stream, X, ldx, Wt, bias, Y, ldy, Ypre, (int)R, NOUT, act);
-    else hipLaunchKernelGGL((k_linear_w<128, 1>), grid, block, 0, stream, X, ldx, Wt, bias, Y, ldy, Ypre, (int)R, NOUT, act);
-    return check_launch("magpo_linear");
-  }
-  const size_t lds = (size_t)64 * (KIN + LDP) * sizeof(float);
-  decltype(&k_linear<192>) k;
-  if (KIN == 192) k = with_lds<k_linear<192>>(lds);
-  else if (KIN == 256) k = with_lds<k_linear<256>>(lds);
-  else if (KIN == 384) k = with_lds<k_linear<384>>(lds);
-  else { set_error("magpo_linear: unsupported KIN"); return MAGPO_EINVAL; }
-  hipLaunchKernelGGL(k, dim3((unsigned)((R + 63) / 64)), dim3(256), lds, stream, X, ldx, Wt, bias, Y, ldy, Ypre, (int)R, NOUT, act);
+  // mask: an INPUT of the backward activations (same shape / stride as Y), never written
+  const bool needs_mask = act == ACT_MASKPOS || act == ACT_TANHBWD;
+  if (needs_mask && !mask) { set_error("magpo_linear: act 4 / 6 (backward masks) need the mask tensor"); return MAGPO_EINVAL; }
+  if (!needs_mask && mask) { set_error("magpo_linear: the pre-activation output was removed; the seventh argument is the mask input of act 4 / 6 and must be null otherwise"); return MAGPO_EINVAL; }
+  // 4 waves per block, 2 when the column groups do not fill blocks of 4 (every wave then has MFMA work);
+  // column groups past NOUT idle in the MFMA part but help loading
+  const int ncg = (NOUT + 31) / 32;
+  const int nw = (ncg % 4 == 0) ? 4 : 2;
+  const int gy = (ncg + nw - 1) / nw;
+  const long ntiles = (R + 31) / 32;
+  long wk2 = 2048 / nw;   // about 2 waves per SIMD; LDS 2 x 32 x (KIN + 4) floats per block
+  // several column blocks per row walker: all of them co-resident (walkers x column blocks <= resident workgroups), so the
+  // column blocks of a walker -- same XCD, since the walker count is a multiple of 8 -- read a tile at about the same
+  // time and the re-reads hit that XCD's L2 instead of HBM (in a second round they would come from HBM again)
+  if (gy >= 3) wk2 /= 2;
+  if (wk2 > ntiles) wk2 = ntiles;
+  // (two-wave blocks -- narrow outputs -- are slower on bf16 triples: 128 -> 20 0.86 vs 1.35 ms)
+  const bool bf3 = variant == 4 && (KIN == 128 || KIN == 192) && nw == 4;
+  const size_t lds = bf3 ? (size_t)2 * 3 * 32 * (KIN + 8) * sizeof(__bf16) : (size_t)2 * 32 * (KIN + LDP) * sizeof(float);
+  decltype(&k_linear_lds<64, 4>) k;
+  if (bf3) k = KIN == 128 ? with_lds<k_linear_lds<128, 4, true>>(lds) : with_lds<k_linear_lds<192, 4, true>>(lds);
+  else if (KIN == 64) k = nw == 4 ? with_lds<k_linear_lds<64, 4>>(lds) : with_lds<k_linear_lds<64, 2>>(lds);
+  else if (KIN == 128) k = nw == 4 ? with_lds<k_linear_lds<128, 4>>(lds) : with_lds<k_linear_lds<128, 2>>(lds);
+  else if (KIN == 192) k = nw == 4 ? with_lds<k_linear_lds<192, 4>>(lds) : with_lds<k_linear_lds<192, 2>>(lds);
+  else if (KIN == 256) k = nw == 4 ? with_lds<k_linear_lds<256, 4>>(lds) : with_lds<k_linear_lds<256, 2>>(lds);
+  else k = nw == 4 ? with_lds<k_linear_lds<384, 4>>(lds) : with_lds<k_linear_lds<384, 2>>(lds);
+  hipLaunchKernelGGL(k, dim3((unsigned)wk2, (unsigned)gy), dim3(64 * nw), lds, stream, X, ldx, Wt, bias, Y, ldy, (int)R, NOUT, act, (const float*)mask);
   return check_launch("magpo_linear");
 }
 

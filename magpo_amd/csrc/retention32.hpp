@@ -15,35 +15,23 @@
 // both row tiles; 64x64 outputs (states) = column tile `wave`, four row tiles (the B fragment is shared by the row tiles).
 //
 // LDS layouts.  A tile is read two ways: by rows (ds_read_b128, lane (idx, kq) takes the float4 at k = kb + 4 kq of row idx) and
-// by columns (ds_read_b32, lane takes element (kb + 4 kq + c, n0 + idx)).  DEFAULT: the +4 pitch (L64 = 68, L32 = L36 = 36 floats) -- the
+// by columns (ds_read_b32, lane takes element (kb + 4 kq + c, n0 + idx)).  The +4 pitch (L64 = 68, L32 = L36 = 36 floats) -- the
 // column reads are conflict-free, the row reads are not: the hardware serves a ds_read_b128 in the lane groups {0-3, 12-15, 20-27},
 // {4-11, 16-19, 28-31}, (+32), a group mixes rows idx of two DIFFERENT kq, i.e. 16-byte slots (row offset + kq) and (row offset + kq + 1),
 // and no pitch keeps those sixteen slots distinct (an odd slot pitch p collides wherever p (i - j) = 1 mod 16, and i - j takes every
 // residue; the column reads need pitch = 4 mod 8 floats): one 2-way slot per group, SQ_LDS_BANK_CONFLICT 1.0e8 per backward launch.
-// -DMAGPO_RET32_SWIZZLE (measured experiment): UNPADDED tiles with the 16-byte slot of a row XORed with the row number -- L64: slot ^= row
-// & 15; L32 (two rows per 256-byte bank row): slot ^= g(row), g = row bits (2, 3, 1) -- are conflict-free for both reads and all writes
-// (counter: 0), and not faster (2.46 vs 2.45 ms; ~70 more registers for the addresses): the conflicts were never the limiter.
-// The P tile of the backward is only ever read by columns and keeps the +4 pitch either way (L36).
+// Measured and removed: UNPADDED tiles with the 16-byte slot of a row XORed with the row number -- L64: slot ^= row & 15; L32 (two rows
+// per 256-byte bank row): slot ^= g(row), g = row bits (2, 3, 1) -- are conflict-free for both reads and all writes (counter: 0), and
+// not faster (2.46 vs 2.45 ms; ~70 more registers for the addresses): the conflicts were never the limiter.
+// The P tile of the backward is only ever read by columns (L36, the same +4 pitch).
 #pragma once
 
 namespace magpo {
 
 constexpr int MAXC32 = 32;       // chunks per sequence whose bookkeeping is built up front
 
-#ifndef MAGPO_RET32_SWIZZLE
 struct L64 { static constexpr int P = 68; static __device__ __forceinline__ int at(int row, int col) { return row * 68 + col; } };
 struct L32 { static constexpr int P = 36; static __device__ __forceinline__ int at(int row, int col) { return row * 36 + col; } };
-#else
-struct L64 {
-  static constexpr int P = 64;
-  static __device__ __forceinline__ int at(int row, int col) { return (row << 6) + ((((col >> 2) ^ row) & 15) << 2) + (col & 3); }
-};
-struct L32 {
-  static constexpr int P = 32;
-  static __device__ __forceinline__ int g(int row) { return (row & 4) | ((row >> 1) & 1) | ((row >> 2) & 2); }
-  static __device__ __forceinline__ int at(int row, int col) { return (row << 5) + ((((col >> 2) ^ g(row)) & 7) << 2) + (col & 3); }
-};
-#endif
 struct L36 {
   static __device__ __forceinline__ int at(int row, int col) { return row * 36 + col; }
 };
@@ -243,7 +231,7 @@ __device__ __forceinline__ void mma16_breg_tr(f32x4 (&acc)[NR], const float* __r
 // the dropped rows / column quads go to the trash tile -- so the number of stores between a chunk's prefetch loads and their first use is
 // a compile-time constant and the wait in front of the stash is vmcnt(#stores), not a drain of the store queue.  (Round 2 stored the
 // untransposed accumulators: 24 four-byte stores per lane and chunk in the backward, each in its own exec-masked block; with the stores
-// removed the kernel ran 15 % faster, scripts/debug/ret32_hooks.sh.)
+// removed the kernel ran 15 % faster, profiles/r03_ret32_timing_hooks.txt.)
 __device__ __forceinline__ void store32x64(float* __restrict__ out, long r0, long ld, const f32x4 (&v)[2], int n0, int idx, int kq, bool full, int nvalid,
                                            int hs, float* __restrict__ trash) {
   const int n = n0 + 4 * kq;
@@ -382,22 +370,6 @@ __global__ __launch_bounds__(256, 3) void k_ret32_fwd(RetArgs a) {
   }
 }
 
-// timing hooks of the backward (debug builds only; results are wrong under them): -DMAGPO_RET32_NOSTORE / _NOLOAD / _NOBAR
-#ifdef MAGPO_RET32_NOSTORE
-#define R32_ST(...) do { if (a.T < 0) store32x64(__VA_ARGS__); } while (0)
-#else
-#define R32_ST(...) store32x64(__VA_ARGS__)
-#endif
-#ifdef MAGPO_RET32_NOBAR
-#define R32_BAR() do { } while (0)
-#else
-#define R32_BAR() __syncthreads()
-#endif
-#ifdef MAGPO_RET32_NOLOAD
-#define R32_LD(X) do { if (a.T < 0) { X; } } while (0)
-#else
-#define R32_LD(X) do { X; } while (0)
-#endif
 template <bool FAST, bool BYROWS>
 __global__ __launch_bounds__(256, 2) void k_ret32_bwd(RetBwdArgs a) {
   extern __shared__ __align__(16) float smem[];
@@ -469,13 +441,13 @@ __global__ __launch_bounds__(256, 2) void k_ret32_bwd(RetBwdArgs a) {
     {
       const int cn = max(c - 1, 0);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) R32_LD(snext[j] = *reinterpret_cast<const float4*>(Sq + (long)cn * 4096 + 16 * j));
+      for (int j = 0; j < 4; ++j) snext[j] = *reinterpret_cast<const float4*>(Sq + (long)cn * 4096 + 16 * j);
     }
     if (TAB) idx_from_lds(ri, rowtab, max(c - 1, 0) * 32);
-    R32_LD(R32_FETCH(pq, q, ldq, rn, nvn));
-    R32_LD(R32_FETCH(pk, k, ldk, rn, nvn));
-    R32_LD(R32_FETCH(pv, v, ldv, rn, nvn));
-    R32_LD(fetch32(pd, a.dr + rn * a.lddr, a.lddr, nvn, w4));
+    R32_FETCH(pq, q, ldq, rn, nvn);
+    R32_FETCH(pk, k, ldk, rn, nvn);
+    R32_FETCH(pv, v, ldv, rn, nvn);
+    fetch32(pd, a.dr + rn * a.lddr, a.lddr, nvn, w4);
     if (by_rows && !TAB) {
       const int cp = max(c - 2, 0);
       fetch_idx32(ri, a.rows, row_base + (long)cp * L, min(Lt, a.T - cp * Lt) * a.A);
@@ -496,7 +468,7 @@ __global__ __launch_bounds__(256, 2) void k_ret32_bwd(RetBwdArgs a) {
         dPs[L32::at(m, j)] = dp[0][i] * w[i];
       }
     }
-    R32_BAR();
+    __syncthreads();
     RP(1);
     // dQ = dP K + beta * (dO S_c^T)
     {
@@ -509,7 +481,7 @@ __global__ __launch_bounds__(256, 2) void k_ret32_bwd(RetBwdArgs a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) a1[r][i] += be * a2[r][i];
       }
-      R32_ST(a.dq, r0, a.lddq, a1, 16 * wave, idx, kq, full, nvalid, a.hs, g_ret_trash);
+      store32x64(a.dq, r0, a.lddq, a1, 16 * wave, idx, kq, full, nvalid, a.hs, g_ret_trash);
     }
     RP(2);
     // dK = dP^T Q + eta * (V G^T)
@@ -523,7 +495,7 @@ __global__ __launch_bounds__(256, 2) void k_ret32_bwd(RetBwdArgs a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) a1[r][i] += et * a2[r][i];
       }
-      R32_ST(a.dk, r0, a.lddk, a1, 16 * wave, idx, kq, full, nvalid, a.hs, g_ret_trash);
+      store32x64(a.dk, r0, a.lddk, a1, 16 * wave, idx, kq, full, nvalid, a.hs, g_ret_trash);
     }
     RP(3);
     // dV = P^T dO + eta * (K G)
@@ -537,7 +509,7 @@ __global__ __launch_bounds__(256, 2) void k_ret32_bwd(RetBwdArgs a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) a1[r][i] += et * a2[r][i];
       }
-      R32_ST(a.dv, r0, a.lddv, a1, 16 * wave, idx, kq, full, nvalid, a.hs, g_ret_trash);
+      store32x64(a.dv, r0, a.lddv, a1, 16 * wave, idx, kq, full, nvalid, a.hs, g_ret_trash);
     }
     RP(4);
     // G <- gamma G + (beta Q)^T dO
@@ -549,7 +521,7 @@ __global__ __launch_bounds__(256, 2) void k_ret32_bwd(RetBwdArgs a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) gn[r][i] = gm * Gs[L64::at(16 * r + 4 * kq + i, n64)];
       mma16<false, false, 32, 4, L64, L64>(gn, Qs, 0, Ds, 16 * wave, idx, kq, meta.beta);
-      R32_BAR();         // every wave is done reading Gs (dK, dV) and this chunk's tiles
+      __syncthreads();   // every wave is done reading Gs (dK, dV) and this chunk's tiles
 #pragma unroll
       for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -562,9 +534,6 @@ __global__ __launch_bounds__(256, 2) void k_ret32_bwd(RetBwdArgs a) {
   }
   RP_FLUSH();
 }
-#undef R32_ST
-#undef R32_BAR
-#undef R32_LD
 #undef R32_FETCH
 
 }  // namespace magpo

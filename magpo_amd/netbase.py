@@ -62,8 +62,8 @@ class NetBase:
         self.L.call("magpo_transpose_pad", W, t, K_, N_, npad, self._st())
         return t
 
-    def lin(self, X, ldx, Wt, bias, Y, ldy, R, KIN, NOUT, act=0, Ypre=None):
-        self.L.call("magpo_linear", X, ldx, Wt, bias, Y, ldy, Ypre, R, KIN, NOUT, act, getattr(self.tuning, self.LINEAR_VARIANT), self._st())
+    def lin(self, X, ldx, Wt, bias, Y, ldy, R, KIN, NOUT, act=0, mask=None):
+        self.L.call("magpo_linear", X, ldx, Wt, bias, Y, ldy, mask, R, KIN, NOUT, act, getattr(self.tuning, self.LINEAR_VARIANT), self._st())
 
     def _groups(self, R):
         """Row slabs of a split weight gradient: no more than one per 256 rows (small minibatches: fewer partials to reduce)."""

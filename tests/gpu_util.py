@@ -50,6 +50,15 @@ class Guard:
         assert not bool(bad.any()), f"{what}: {int(bad.sum())} elements outside the owned block were overwritten"
 
 
+def transpose_pad(L, st, W):
+    """Wt [N padded to 32][K] = W[K][N]^T on the device, the weight layout of magpo_linear."""
+    K, N = W.shape
+    Np = (N + 31) // 32 * 32
+    Wt = torch.empty(Np, K, device=DEV)
+    L.call("magpo_transpose_pad", W, Wt, K, N, Np, st)
+    return Wt
+
+
 def ptr_table(tensors):
     return np.array([0 if t is None else t.data_ptr() for t in tensors], dtype=np.uint64)
 

@@ -49,6 +49,21 @@ def test_no_setters_and_no_environment_reads(built):
         built.call("magpo_wgrad", None, 64, None, 64, 1, 64, 64, 64, None, None, None, 1, 1.0, 0, 1, None)
 
 
+def test_linear_validates_mask_and_width_before_any_launch(built):
+    """The seventh argument of magpo_linear is the mask INPUT of act 4 / 6 only: required there, rejected (not silently ignored) for every
+    other act now that the pre-activation output is gone; KIN outside {64, 128, 192, 256, 384} is rejected.  All of it before a pointer
+    is touched, so a host buffer stands in for the tensor."""
+    buf = (ctypes.c_float * 4)()
+    for act in (0, 3, 5):
+        with pytest.raises(ValueError, match="pre-activation output was removed"):
+            built.call("magpo_linear", None, 64, None, None, None, 64, ctypes.addressof(buf), 1, 64, 64, act, 0, None)
+    for act in (4, 6):
+        with pytest.raises(ValueError, match="mask"):
+            built.call("magpo_linear", None, 64, None, None, None, 64, None, 1, 64, 64, act, 0, None)
+    with pytest.raises(ValueError, match="KIN"):
+        built.call("magpo_linear", None, 320, None, None, None, 64, None, 1, 320, 64, 0, 0, None)
+
+
 def test_no_torch_types_and_plain_c_header():
     text = open(_lib.HEADER).read()
     assert "torch" not in text and "at::" not in text and 'extern "C"' in text

@@ -1,5 +1,5 @@
 """Every entry point of include/magpo.h is called by name in some GPU test module, or is listed here with the test that reaches it
-through a host wrapper.  A new entry point without a primitive test fails this module on the CPU."""
+through a host wrapper (the product's, or the one helper shared by the GPU modules in tests/gpu_util.py).  A new entry point without a primitive test fails this module on the CPU."""
 import glob
 import os
 import re
@@ -24,6 +24,7 @@ INDIRECT = {
     "magpo_mpe_step": "tests.test_mpe_gpu::test_mpe_env_matches_restatement",
     "magpo_sable_act": "tests.test_act_instances_gpu::test_forced_instance_equals_kernel_composition_under_graph_replay",   # SableGuider.act_fused
     "magpo_act_weight_layout": "tests.test_act_instances_gpu::test_forced_instance_equals_kernel_composition_under_graph_replay",   # SableGuider.refresh
+    "magpo_transpose_pad": "tests.test_kernels_gpu::test_linear_shared_tile",                      # tests.gpu_util.transpose_pad (exactness asserted there)
 }
 
 

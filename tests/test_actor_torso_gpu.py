@@ -13,6 +13,7 @@ from oracle import coordsum as ocs
 from oracle import learner as olearn
 from oracle import networks as onets
 from oracle import prng as oprng
+from tests.gpu_util import transpose_pad
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -77,30 +78,20 @@ def test_layernorm_act_rejects_bad_shapes(L, stream):
         L.call("magpo_ln_act_fwd", x, 128, x[0], x, 128, x, 128, x[:, 0], 4, 128, 2, stream)
 
 
-def _tp(L, st, W):
-    K, N = W.shape
-    Np = (N + 31) // 32 * 32
-    Wt = torch.empty(Np, K, device=DEV)
-    L.call("magpo_transpose_pad", W, Wt, K, N, Np, st)
-    return Wt
-
-
-@pytest.mark.parametrize("KIN,NOUT,R,variant,pre", [(64, 256, 130, 0, False), (128, 128, 77, 0, True), (256, 64, 65, 0, False),
-                                                    (192, 192, 300, 0, False), (128, 384, 1000, 4, False), (64, 64, 33, 0, True)])
-def test_linear_tanh_epilogue(L, stream, KIN, NOUT, R, variant, pre):
+@pytest.mark.parametrize("KIN,NOUT,R,variant", [(64, 256, 130, 0), (128, 128, 77, 0), (256, 64, 65, 0),
+                                                (192, 192, 300, 0), (128, 384, 1000, 4), (64, 64, 33, 0)])
+def test_linear_tanh_epilogue(L, stream, KIN, NOUT, R, variant):
     g = torch.Generator().manual_seed(KIN + NOUT)
     X = torch.randn(R, KIN, generator=g); W = torch.randn(KIN, NOUT, generator=g) / math.sqrt(KIN); b = torch.randn(NOUT, generator=g)
-    Y = torch.zeros(R, NOUT, device=DEV); Yp = torch.zeros(R, NOUT, device=DEV) if pre else None
-    assert L.call("magpo_linear", X.to(DEV), KIN, _tp(L, stream, W.to(DEV)), b.to(DEV), Y, NOUT, Yp, R, KIN, NOUT, 5, variant, stream) == 0
+    Y = torch.zeros(R, NOUT, device=DEV)
+    assert L.call("magpo_linear", X.to(DEV), KIN, transpose_pad(L, stream, W.to(DEV)), b.to(DEV), Y, NOUT, None, R, KIN, NOUT, 5, variant, stream) == 0
     z = X.double() @ W.double() + b.double()
     close(Y, torch.tanh(z), what="tanh")
-    if pre:
-        close(Yp, z, what="pre-activation")
 
 
 @pytest.mark.parametrize("KIN,NOUT,R,variant", [(64, 256, 130, 0), (128, 128, 77, 0), (384, 128, 70, 0), (384, 256, 129, 0), (256, 64, 4001, 4)])
 def test_linear_fused_tanh_backward(L, stream, KIN, NOUT, R, variant):
-    """act 6: dX = (dY W^T) * (1 - y^2) with y (the forward's tanh output) in the Ypre slot, on the shared-tile kernels."""
+    """act 6: dX = (dY W^T) * (1 - y^2) with y (the forward's tanh output) as the mask argument, on the shared-tile kernels."""
     g = torch.Generator().manual_seed(3 * KIN + NOUT)
     dY = torch.randn(R, KIN, generator=g); W = torch.randn(NOUT, KIN, generator=g) / math.sqrt(KIN)   # natural [NOUT][KIN]: dX = dY W^T
     y = torch.tanh(torch.randn(R, NOUT, generator=g))

@@ -14,6 +14,7 @@ from oracle import coordsum as ocs
 from oracle import learner as olearn
 from oracle import networks as onets
 from oracle import prng as oprng
+from tests.gpu_util import transpose_pad
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -33,37 +34,6 @@ def close(a, b, rtol=2e-5, atol=2e-6, what=""):
     err = (a - b).abs().max().item()
     ref = b.abs().max().item()
     assert err <= atol + rtol * ref, f"{what}: max err {err:.3e} vs ref scale {ref:.3e}"
-
-
-def transpose_pad(L, st, W):
-    K, N = W.shape
-    Np = (N + 31) // 32 * 32
-    Wt = torch.empty(Np, K, device=DEV)
-    L.call("magpo_transpose_pad", W, Wt, K, N, Np, st)
-    return Wt
-
-
-@pytest.mark.parametrize("KIN,NOUT,R,act", [(64, 64, 200, 0), (64, 256, 130, 2), (128, 384, 64, 0), (256, 64, 77, 0),
-                                             (64, 20, 100, 0), (128, 128, 300, 1), (192, 64, 65, 0), (384, 128, 70, 0)])
-def test_linear(L, stream, KIN, NOUT, R, act):
-    g = torch.Generator().manual_seed(1)
-    X = torch.randn(R, KIN, generator=g)
-    W = torch.randn(KIN, NOUT, generator=g) / math.sqrt(KIN)
-    b = torch.randn(NOUT, generator=g)
-    Xd, Wd, bd = dev(X), dev(W), dev(b)
-    Wt = transpose_pad(L, stream, Wd)
-    close(Wt[:NOUT], W.T, 0, 0, "transpose")
-    ld = (NOUT + 3) // 4 * 4
-    Y = torch.zeros(R, ld, device=DEV)
-    Yp = torch.zeros(R, ld, device=DEV)
-    L.call("magpo_linear", Xd, KIN, Wt, bd, Y, ld, Yp, R, KIN, NOUT, act, 0, stream)
-    ref = X.double() @ W.double() + b.double()
-    close(Yp[:, :NOUT], ref, what="pre")
-    if act == 1:
-        ref = torch.relu(ref)
-    elif act == 2:
-        ref = torch.nn.functional.gelu(ref, approximate="tanh")
-    close(Y[:, :NOUT], ref, what="act")
 
 
 @pytest.mark.parametrize("KIN,NOUT,R", [(64, 64, 1000), (64, 256, 333), (128, 384, 200), (64, 20, 500), (256, 64, 100),
@@ -87,14 +57,16 @@ def test_wgrad(L, stream, KIN, NOUT, R):
 
 @pytest.mark.parametrize("KIN,NOUT,R,act", [(64, 64, 203, 0), (64, 256, 130, 1), (64, 192, 97, 0), (64, 20, 100, 0), (128, 384, 1000, 0),
                                              (128, 128, 333, 1), (128, 96, 65, 0), (256, 64, 77, 0), (192, 64, 65, 2), (384, 128, 70, 0),
-                                             (384, 100, 31, 0)])
+                                             (384, 100, 31, 0), (64, 64, 200, 0), (64, 256, 130, 2), (128, 384, 64, 0), (128, 128, 300, 1),
+                                             (192, 64, 65, 0)])
 def test_linear_shared_tile(L, stream, KIN, NOUT, R, act):
-    """k_linear_lds (no pre-activation copy requested): full and ragged tiles / column groups, 2- and 4-wave blocks."""
+    """k_linear_lds: full and ragged tiles / column groups, 2- and 4-wave blocks; magpo_transpose_pad is exact."""
     g = torch.Generator().manual_seed(11)
     X = torch.randn(R, KIN, generator=g)
     W = torch.randn(KIN, NOUT, generator=g) / math.sqrt(KIN)
     b = torch.randn(NOUT, generator=g)
     Wt = transpose_pad(L, stream, dev(W))
+    close(Wt[:NOUT], W.T, 0, 0, "transpose")
     ld = (NOUT + 3) // 4 * 4
     Y = torch.full((R + 1, ld), 7.0, device=DEV)   # guard row: nothing may be written past R
     L.call("magpo_linear", dev(X), KIN, Wt, dev(b), Y, ld, None, R, KIN, NOUT, act, 0, stream)
@@ -144,7 +116,7 @@ def test_linear_bf16_triples_keep_fp32_accuracy(L, stream):
 
 
 def test_linear_relu_mask_epilogue(L, stream):
-    """act 4: dX = (dY W^T) masked by the forward activation passed in the Ypre slot (ReLU backward fused into the GEMM)."""
+    """act 4: dX = (dY W^T) masked by the forward activation passed as the mask argument (ReLU backward fused into the GEMM)."""
     KIN, NOUT, R = 64, 128, 173
     g = torch.Generator().manual_seed(14)
     X = torch.randn(R, KIN, generator=g)

@@ -17,7 +17,7 @@ from oracle import learner as olearn
 from oracle import networks as onets
 from oracle import prng as oprng
 from tests import kernel_refs as kr
-from tests.gpu_util import DEV, PAD, UNSET_INT, Guard, check, check_sum, dev
+from tests.gpu_util import DEV, PAD, UNSET_INT, Guard, check, check_sum, dev, transpose_pad
 
 pytestmark = pytest.mark.gpu
 D = torch.float64
@@ -478,22 +478,16 @@ def test_wgrad_krows(L, stream, KIN, NOUT, R, G, krows):
     check_sum(f"wgrad krows={krows} {KIN}x{NOUT} dW", dW.out, w64, w32); check_sum(f"wgrad krows={krows} {KIN}x{NOUT} db", db.out[0], b64, b32)
 
 
-@pytest.mark.parametrize("KIN,NOUT,R,pre", [(64, 64, 203, False), (128, 100, 65, False), (64, 256, 130, True), (256, 64, 77, True)])
-def test_linear_swish(L, stream, KIN, NOUT, R, pre):
-    """act = 3: Y = swish(X W + b), on the shared-tile kernels (no pre-activation copy) and on the kernels that also write Ypre."""
+@pytest.mark.parametrize("KIN,NOUT,R", [(64, 64, 203), (128, 100, 65), (64, 256, 130), (256, 64, 77)])
+def test_linear_swish(L, stream, KIN, NOUT, R):
+    """act = 3: Y = swish(X W + b) on the shared-tile kernels."""
     g = torch.Generator().manual_seed(23)
     X, W, b = torch.randn(R, KIN, generator=g), torch.randn(KIN, NOUT, generator=g) / math.sqrt(KIN), torch.randn(NOUT, generator=g)
-    Np = (NOUT + 31) // 32 * 32
-    Wt = torch.empty(Np, KIN, device=DEV)
-    L.call("magpo_transpose_pad", dev(W), Wt, KIN, NOUT, Np, stream)
+    Wt = transpose_pad(L, stream, dev(W))
     ld = kr.ceil4(NOUT)
-    Y, Yp = Guard(R, NOUT, ld), Guard(R, NOUT, ld)
-    L.call("magpo_linear", dev(X), KIN, Wt, dev(b), Y, ld, Yp if pre else None, R, KIN, NOUT, 3, 0, stream)
+    Y = Guard(R, NOUT, ld)
+    L.call("magpo_linear", dev(X), KIN, Wt, dev(b), Y, ld, None, R, KIN, NOUT, 3, 0, stream)
     _sync()
-    Y.check("linear swish Y"); Yp.check("linear swish Ypre", None if pre else torch.zeros(R, dtype=torch.bool))
+    Y.check("linear swish Y")
     ref = X.double() @ W.double() + b.double()
     check(f"linear swish {KIN}x{NOUT} R={R} Y", Y.out, onets.swish(ref), kr.local_bound(onets.swish(ref)))
-    if pre:
-        check(f"linear swish {KIN}x{NOUT} R={R} Ypre", Yp.out, ref, kr.local_bound(ref))
-    else:
-        assert bool(torch.isnan(Yp.out).all())
