@@ -305,6 +305,20 @@ int magpo_gru_carry(const float* xi, const float* Wht, const float* b_hn, const 
 int magpo_gru_scan_bwd(const float* gates, const float* hprev, const unsigned char* reset, const float* dhs,
                        const float* Wh, float* dg, float* slab_bhn, int nseq, int T, int A,
                        int split_bf16, int block_rows, magpo_stream_t stream);
+/* ONE GRU cell step, for one or two networks in a single launch (csrc/gru_step.hip; the acting step of recurrent PPO, rec_mappo.py:96-141):
+ * h_out = GRUCell(h_in zeroed where reset, emb), the recurrence above with the input projection emb W_i + b_i formed inside the kernel (no xi
+ * buffer).  dims_host[3] = {nnets (1 or 2), D of network 0, D of network 1}; D = width of emb, 64 / 128 / 192 / 256, and may differ between the
+ * networks.  ptrs_host[7 nnets] (device pointers), per network: emb [R][D], Wit [384][D], bi [384], Wht [384][128], b_hn [128], h_in [R][128],
+ * h_out [R][128] (Wit / Wht as magpo_transpose_pad writes them; h_out may be h_in).  reset [ceil(R / A)] u8: row r belongs to env r / A.
+ * Grid (ceil(R / 64), nnets); rows beyond R are never written.  Rejected before any launch: R < 1, A < 1, nnets not 1 or 2, nptrs != 7 nnets,
+ * a D outside the set, a null pointer. */
+int magpo_gru_cell_step(const int* dims_host, const void* const* ptrs_host, int nptrs, const unsigned char* reset, int R,
+                        int A, magpo_stream_t stream);
+/* observation.global_state of the centralised critic (mava/wrappers/matrax.py:128-131, jumanji.py:61-67): out [N A][ld], row (n, a) = the
+ * concatenation over agents j of obs[(n, j)][id_cols .. id_cols + F_raw) (the raw agent views behind the id_cols leading agent-id columns of the
+ * stored rows, row stride ldo), the same for every a, zero from column A F_raw to ld.  ld is 64 or 128 and A F_raw <= ld. */
+int magpo_global_state(const float* obs, long ldo, int id_cols, int F_raw, float* out, int ld, int N, int A,
+                       magpo_stream_t stream);
 
 /* ---- K2 sampling, K5 GAE, K6 shuffle/layout, K9 losses (decode.py:128-149; multistep.py:24-68; rec_magpo.py:222-370,439-462) ---- */
 int magpo_sample_categorical(const float* logits, long ld, const unsigned char* mask, long mask_stride,

@@ -54,6 +54,76 @@ class SystemConfig:
     micro_batches: int = 1
 
 
+def split_setup_keys(L, dev, st, key: np.ndarray, total: int):
+    """learner_setup's key layout (rec_magpo.py:642-660 = rec_mappo.py:495-513): split(key, total) on the device; row 0 is split once more on
+    the host into (set-up key, the ONE step key every group shares).  Returns (device keys [total, 2] i32, set-up key, step key)."""
+    kd = torch.from_numpy(np.ascontiguousarray(key, np.uint32).view(np.int32)).to(dev)
+    allk = torch.empty(total, 2, dtype=torch.int32, device=dev)
+    L.call("magpo_threefry_split", kd, allk, total, st)
+    ks = host_split(allk[0].cpu().numpy().view(np.uint32), 2)
+    return allk, ks[0], ks[1]
+
+
+def setup_env_groups(L, dev, st, groups, key: np.ndarray, N: int, n_groups: int, group: int) -> np.ndarray:
+    """What every system's set-up does with its env groups (objects with ``env``, ``traj`` and ``key``): reset keys are rows 1.. of
+    split(key, n_groups * N + 1) laid out row-major over (group, env), ``group`` = global index of the first local group; slot 0 of the
+    trajectory takes the reset observation and done = 0; ONE step key is shared by every group.  Returns the set-up key."""
+    if group < 0 or group + len(groups) > n_groups:   # (a short key table would send the env-reset kernel out of bounds)
+        raise ValueError(f"setup: this learner holds {len(groups)} env group(s) starting at group {group}, but the job has n_groups={n_groups}")
+    allk, setup_key, step_key = split_setup_keys(L, dev, st, key, n_groups * N + 1)
+    for gi, g in enumerate(groups):
+        env_keys = allk[1 + (group + gi) * N: 1 + (group + gi + 1) * N].contiguous()
+        g.env.reset(env_keys, g.traj["obs"][0], g.traj["step_count"][0], None if g.traj["mask"] is None else g.traj["mask"][0])
+        g.traj["done"][0].zero_()
+        g.key = step_key.copy()
+    return setup_key
+
+
+def jax_permutation(L, dev, st, key: np.ndarray, n: int) -> torch.Tensor:
+    """jax.random.permutation(key, n) on the device: rounds of a stable sort by 32 random bits."""
+    rounds = int(math.ceil(3 * math.log(max(1, n)) / math.log(2 ** 32 - 1)))
+    x = torch.arange(n, dtype=torch.int32, device=dev)
+    bits = torch.empty(n, dtype=torch.int32, device=dev)
+    for _ in range(rounds):
+        ks = host_split(key, 2)
+        key, sub = ks[0], ks[1]
+        kd = torch.from_numpy(sub.view(np.int32).copy()).to(dev)
+        L.call("magpo_threefry_random_bits", kd, bits, n, st)
+        order = torch.sort(bits.to(torch.int64) & 0xFFFFFFFF, stable=True).indices
+        x = x[order]
+    return x.contiguous()
+
+
+class AdvStats:
+    """The [mean, 1 / (std + eps)] pair a loss kernel normalises the advantages of a minibatch with (rec_magpo.py:283,356; rec_sable.py:199;
+    rec_mappo.py:193), per group when several groups train as one batch of sequences.  Owns its small device buffers."""
+
+    def __init__(self, L, dev):
+        self.L, self.dev = L, dev
+        self.one = torch.zeros(2, dtype=torch.float32, device=dev)
+        self.per_group = None
+        self.ident = None
+
+    def __call__(self, m, U: int, adv_stats: Optional[torch.Tensor], ws64: torch.Tensor, st) -> torch.Tensor:
+        R = m["R"]
+        R1 = R // U
+        if U == 1:
+            if adv_stats is None:
+                self.L.call("magpo_adv_moments", m["adv"], R, ws64, self.one, st)
+            return self.one if adv_stats is None else adv_stats[0]
+        # per-group statistics, applied in place with the loss kernel's own expression (adv - mean) * rstd; identity stats after
+        if self.per_group is None or self.per_group.shape[0] != U:
+            self.per_group = torch.zeros(U, 2, device=self.dev)
+            self.ident = torch.tensor([0.0, 1.0], device=self.dev)
+        su = self.per_group if adv_stats is None else adv_stats
+        if adv_stats is None:
+            for u in range(U):
+                self.L.call("magpo_adv_moments", m["adv"][u * R1:(u + 1) * R1], R1, ws64, su[u], st)
+        a2 = m["adv"].view(U, R1)
+        a2.sub_(su[:, 0:1]).mul_(su[:, 1:2])
+        return self.ident
+
+
 class EnvGroup:
     """Per-group rollout state: envs, trajectory, retention / GRU states, PRNG key.  A group is the
     reference's (device, update-batch) replica (rec_magpo.py:519, :648-653); all groups of a process share
@@ -165,7 +235,8 @@ class MagpoLearner:
         # optimiser state (optax adam: count, mu, nu) lives in the two ClipAdam objects: g_mu / g_nu / g_count ... below are views of it
         self.ws64 = torch.zeros(8 * 1024, dtype=torch.float64, device=device)
         self.gnorm = f32(2)
-        self.adv_stats = f32(2)
+        self._adv = AdvStats(self.L, device)
+        self.adv_stats = self._adv.one
         self._mb: Dict[str, torch.Tensor] = {}
         # First-layer class tables (csrc/classtab.hip): a wrapped CoordSum token is one of A*maxval*npos distinct inputs, so the
         # layers in front of the GRU / of the first retention run on the distinct rows only.  MAGPO_CLASS_TABLES=0 = dense path.
@@ -211,20 +282,8 @@ class MagpoLearner:
         this process's first group.  Reset keys are rows 1.. of split(key, n_groups*N + 1) laid out row-major
         over (group, env); ONE step key is shared by every group (rec_magpo.py:660-671)."""
         N = self.N
-        if group < 0 or group + len(self.groups) > n_groups:   # (a short key table would send the env-reset kernel out of bounds)
-            raise ValueError(f"setup: this learner holds {len(self.groups)} env group(s) starting at group {group}, but the job has n_groups={n_groups}")
-        total = n_groups * N + 1
-        kd = torch.from_numpy(np.ascontiguousarray(key, np.uint32).view(np.int32)).to(self.dev)
-        allk = torch.empty(total, 2, dtype=torch.int32, device=self.dev)
-        self.L.call("magpo_threefry_split", kd, allk, total, self._st())
-        key0 = allk[0].cpu().numpy().view(np.uint32)
-        ks = host_split(key0, 2)
-        self.setup_key = ks[0]
-        for gi, g in enumerate(self.groups):
-            env_keys = allk[1 + (group + gi) * N: 1 + (group + gi + 1) * N].contiguous()
-            g.env.reset(env_keys, g.traj["obs"][0], g.traj["step_count"][0], None if g.traj["mask"] is None else g.traj["mask"][0])
-            g.traj["done"][0].zero_()
-            g.key = ks[1].copy()
+        self.setup_key = setup_env_groups(self.L, self.dev, self._st(), self.groups, key, N, n_groups, group)
+        for g in self.groups:
             for h in g.sable_hs:
                 h.zero_()
             if self.has_actor:
@@ -385,17 +444,7 @@ class MagpoLearner:
 
     # ------------------------------------------------------------------ shuffles (jax.random.permutation)
     def _permutation(self, key: np.ndarray, n: int) -> torch.Tensor:
-        rounds = int(math.ceil(3 * math.log(max(1, n)) / math.log(2 ** 32 - 1)))
-        x = torch.arange(n, dtype=torch.int32, device=self.dev)
-        bits = torch.empty(n, dtype=torch.int32, device=self.dev)
-        for _ in range(rounds):
-            ks = host_split(key, 2)
-            key, sub = ks[0], ks[1]
-            kd = torch.from_numpy(sub.view(np.int32).copy()).to(self.dev)
-            self.L.call("magpo_threefry_random_bits", kd, bits, n, self._st())
-            order = torch.sort(bits.to(torch.int64) & 0xFFFFFFFF, stable=True).indices
-            x = x[order]
-        return x.contiguous()
+        return jax_permutation(self.L, self.dev, self._st(), key, n)
 
     # ------------------------------------------------------------------ one minibatch (rec_magpo.py:217-435)
     def _gather(self, groups: List[int], env_idx: torch.Tensor, agent_perm: torch.Tensor):
@@ -528,25 +577,8 @@ class MagpoLearner:
         return m, hidx, U, gcl, acl
 
     def _minibatch_stats(self, m, U: int, adv_stats: Optional[torch.Tensor]) -> torch.Tensor:
-        """The [mean, 1 / (std + eps)] pair the loss kernel normalises the advantages with (rec_magpo.py:283,356; rec_sable.py:199)."""
-        R, st = m["R"], self._st()
-        R1 = R // U
-        if U == 1:
-            if adv_stats is None:
-                self.L.call("magpo_adv_moments", m["adv"], R, self.ws64, self.adv_stats, st)
-            stats = self.adv_stats if adv_stats is None else adv_stats[0]
-        else:   # per-group statistics, applied in place with the loss kernel's own expression (adv - mean) * rstd; identity stats after
-            if getattr(self, "_adv_stats_u", None) is None or self._adv_stats_u.shape[0] != U:
-                self._adv_stats_u = torch.zeros(U, 2, device=self.dev)
-                self._adv_ident = torch.tensor([0.0, 1.0], device=self.dev)
-            su = self._adv_stats_u if adv_stats is None else adv_stats
-            if adv_stats is None:
-                for u in range(U):
-                    self.L.call("magpo_adv_moments", m["adv"][u * R1:(u + 1) * R1], R1, self.ws64, su[u], st)
-            a2 = m["adv"].view(U, R1)
-            a2.sub_(su[:, 0:1]).mul_(su[:, 1:2])
-            stats = self._adv_ident
-        return stats
+        """The [mean, 1 / (std + eps)] pair the loss kernel normalises the advantages with (AdvStats)."""
+        return self._adv(m, U, adv_stats, self.ws64, self._st())
 
     def apply_grads(self, grad_scale: float = 1.0):
         """optax clip_by_global_norm + adam + apply_updates on both flat buffers (rec_magpo.py:412-420): the two update functions."""

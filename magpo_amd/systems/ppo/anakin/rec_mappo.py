@@ -1,0 +1,19 @@
+"""rec_mappo system entry point on MI355X -- drop-in for mava/systems/ppo/anakin/rec_mappo.py: a GRU actor and a centralised GRU critic under PPO.
+
+Same public names and call contract as the reference system file (get_learner_fn, learner_setup, run_experiment, hydra_entry_point); the
+implementation is shared with rec_ippo (magpo_amd/systems/ppo/anakin/rec_ppo.py).
+
+    python -m magpo_amd.systems.ppo.anakin.rec_mappo env=coordsum env/scenario=3x30-50 arch.num_envs=64
+"""
+from magpo_amd.systems.ppo.anakin.rec_ppo import make_system
+from magpo_amd.systems.ppo.types import HiddenStates, OptStates, Params, RNNLearnerState, RNNPPOTransition  # noqa: F401
+from magpo_amd.types import ExperimentOutput  # noqa: F401
+
+_system = make_system("rec_mappo", centralised=True)
+get_learner_fn = _system.get_learner_fn
+learner_setup = _system.learner_setup
+run_experiment = _system.run_experiment
+hydra_entry_point = _system.hydra_entry_point
+
+if __name__ == "__main__":
+    hydra_entry_point()

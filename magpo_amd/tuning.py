@@ -18,6 +18,9 @@ Environment variables are read HERE, once, when the default instance is built (A
                                 (profiles/r03_sweep_return_at_10M.md) -- not understood, so not a default
     MAGPO_WGRAD_BF3=1           the 128 x 384 weight gradient on bf16 triples: opt-in, its accumulation error is 1.2 x the fp32-MFMA kernel's
     MAGPO_ACT_EPW=4|8|16        envs per wave of the fused acting kernel (default: by size)
+    MAGPO_PPO_FUSED_STEP=0|1    acting step of rec_ippo / rec_mappo: 1 = both GRU cells in one magpo_gru_cell_step launch (csrc/gru_step.hip), 0 = the
+                                composed GruActor.step of each network (magpo_linear for xi + a T = 1 scan).  Same function, fp32 summation order differs.
+                                Default: see Tuning.ppo_fused_step
 """
 from __future__ import annotations
 
@@ -34,6 +37,7 @@ class Tuning:
     actor_linear_variant: int = 0 # magpo_linear of the GRU actor
     wgrad_variant: int = 0        # magpo_wgrad (0, or 64 = bf16 triples for 128 x 384)
     act_envs_per_wave: int = 0    # magpo_sable_act dims[11]
+    ppo_fused_step: bool = True   # critic.step_pair: magpo_gru_cell_step (True) or the composed step of each network (False)
 
     @classmethod
     def from_env(cls, env=None) -> "Tuning":
@@ -46,4 +50,5 @@ class Tuning:
         t.linear_variant = t.actor_linear_variant = 4 if on("MAGPO_LINEAR_BF3") else 0
         t.wgrad_variant = 64 if on("MAGPO_WGRAD_BF3") else 0
         t.act_envs_per_wave = int(e["MAGPO_ACT_EPW"]) if e.get("MAGPO_ACT_EPW") in ("4", "8", "16") else 0
+        t.ppo_fused_step = e["MAGPO_PPO_FUSED_STEP"] == "1" if e.get("MAGPO_PPO_FUSED_STEP") in ("0", "1") else cls().ppo_fused_step
         return t

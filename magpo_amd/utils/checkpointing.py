@@ -222,6 +222,12 @@ def restore_learner_state(path: str, device="cuda", rank: int = 0, world: int = 
         from ..systems.sable.types import HiddenStates as SableHS, LearnerState as SableLearnerState
         return SableLearnerState(dev(st["params"]), dev(st["opt_states"]), st["key"], dev(st["env_state"]), dev(st["timestep"]),
                                  SableHS(**dev(hs))), int(ck["timestep"])
+    if "critic_params" in st["params"]:   # the recurrent PPO systems (systems/ppo/types.py: RNNLearnerState)
+        from ..systems.ppo import types as ppo
+        return ppo.RNNLearnerState(ppo.Params(dev(st["params"]["actor_params"]), dev(st["params"]["critic_params"])),
+                                   ppo.OptStates(dev(st["opt_states"]["actor_opt_state"]), dev(st["opt_states"]["critic_opt_state"])),
+                                   st["key"], dev(st["env_state"]), dev(st["timestep"]), dev(st["dones"]),
+                                   ppo.HiddenStates(dev(hs["policy_hidden_state"]), dev(hs["critic_hidden_state"]))), int(ck["timestep"])
     state = GPOLearnerState(Params(dev(st["params"]["guider_params"]), dev(st["params"]["actor_params"])),
                             OptStates(dev(st["opt_states"]["guider_opt_state"]), dev(st["opt_states"]["actor_opt_state"])),
                             st["key"], dev(st["env_state"]), dev(st["timestep"]), dev(st["dones"]),

@@ -266,8 +266,19 @@ FACTORIES = {"CoordSum": make_coordsum_env, "LevelBasedForaging": make_lbf_env, 
              "VectorConnector": make_vector_connector_env, "MPE": make_mpe_env}
 
 
-def make(config):
+def make(config, add_global_state: bool = False):
+    """``add_global_state`` (make_env.py:202-218,288-315; rec_mappo.py:558): the centralised critic's observation.global_state -- the
+    concatenation over agents of the raw agent views, taken before the AgentIDWrapper and tiled to every agent.  On the HIP path the
+    learner forms those rows from the stored observation rows (magpo_global_state) whenever it needs them, so the flag only checks that
+    the env supports it (num_agents * raw features <= 128) and marks the envs (``env.add_global_state``, ``env.global_state_dim``)."""
     env_name = config.env.env_name
     if env_name not in FACTORIES:
         raise ValueError(f"{env_name} is not a supported environment.")
-    return FACTORIES[env_name](config)
+    env, eval_env = FACTORIES[env_name](config)
+    if add_global_state:
+        from ..critic import global_state_ld
+        raw = env.cfg.obs_dim - env.cfg.num_agents
+        global_state_ld(env.cfg.num_agents, raw)   # NotImplementedError that names the limit (Robot Warehouse and anything wider)
+        for e in (env, eval_env):
+            e.add_global_state, e.global_state_dim = True, env.cfg.num_agents * raw
+    return env, eval_env
