@@ -11,152 +11,45 @@ scalars, rec_magpo.py:441-462 becomes index arithmetic):
               episode"), action/value/log_prob/reward/adv/targets [T,N,A]
   states      3 x [N,64,64] fp32 retention states, policy hidden [N*A,128]
   minibatch   rows (j, t, a') sequence-major, R = mb*T*A
+
+Groups, set-up, the rollout's graph capture, the gather and the group dispatch of an optimisation step are AnakinLearner's (anakin.py).
 """
 from __future__ import annotations
 
-import math
-from dataclasses import dataclass
-from typing import Callable, Dict, List, Optional, Tuple
+import os
+from typing import Callable, List, Optional
 
-import numpy as np
 import torch
 
-from ._lib import lib
+from ._lib import lib  # noqa: F401
 from .actor import GruActor
-# the environments live in envs.py; their names are re-exported here for the callers that import them from the learner
+# what every learner shares lives in anakin.py, the environments in envs.py; their names are re-exported here for the callers that
+# import them from the learner
+from .anakin import AdvStats, AnakinLearner, Group, SystemConfig, jax_permutation, setup_env_groups, split_setup_keys  # noqa: F401
 from .envs import (ConnectorEnvBatch, CoordSumConfig, CoordSumEnvBatch, LbfConfig, LbfEnvBatch, MpeConfig, MpeEnvBatch, RwareConfig,  # noqa: F401
                    RwareEnvBatch, VectorConnectorConfig, host_split, make_env_batch, net_obs, obs_row_stride, prng_key)
+from .optim import ClipAdam
+from .params import FlatParams, actor_layout, guider_layout
 from .sable import SableGuider
+from .tuning import Tuning
 
 
-@dataclass
-class SystemConfig:
-    rollout_length: int = 128
-    ppo_epochs: int = 4
-    num_minibatches: int = 2
-    gamma: float = 0.99
-    gae_lambda: float = 0.95
-    clip_eps: float = 0.2
-    ent_coef: float = 0.01
-    vf_coef: float = 0.5
-    max_grad_norm: float = 0.5
-    clip_gpo: float = 1.5
-    alpha: float = 1.0
-    actor_lr: float = 2.5e-4
-    # make_learning_rate (mava/utils/training.py:20-64): linear decay lr * (1 - (count // (ppo_epochs * num_minibatches)) / num_updates)
-    # with the optimiser step count BEFORE the step; lr_num_updates is config.system.num_updates as the schedule reads it when the learner
-    # is TRACED (first learn() call), i.e. the value check_total_timesteps derived: the system file refreshes it on every learn() call
-    decay_learning_rates: bool = False
-    lr_num_updates: int = 1000
-    # not a reference key: every minibatch is trained in this many equal slabs of sequences whose gradients are accumulated before the
-    # ONE optimiser step (same gradient up to fp32 summation order; advantage statistics stay those of the whole minibatch).
-    # Activations in HBM scale with the slab, so large teams run at the reference's num_minibatches within the memory of one GPU.
-    micro_batches: int = 1
-
-
-def split_setup_keys(L, dev, st, key: np.ndarray, total: int):
-    """learner_setup's key layout (rec_magpo.py:642-660 = rec_mappo.py:495-513): split(key, total) on the device; row 0 is split once more on
-    the host into (set-up key, the ONE step key every group shares).  Returns (device keys [total, 2] i32, set-up key, step key)."""
-    kd = torch.from_numpy(np.ascontiguousarray(key, np.uint32).view(np.int32)).to(dev)
-    allk = torch.empty(total, 2, dtype=torch.int32, device=dev)
-    L.call("magpo_threefry_split", kd, allk, total, st)
-    ks = host_split(allk[0].cpu().numpy().view(np.uint32), 2)
-    return allk, ks[0], ks[1]
-
-
-def setup_env_groups(L, dev, st, groups, key: np.ndarray, N: int, n_groups: int, group: int) -> np.ndarray:
-    """What every system's set-up does with its env groups (objects with ``env``, ``traj`` and ``key``): reset keys are rows 1.. of
-    split(key, n_groups * N + 1) laid out row-major over (group, env), ``group`` = global index of the first local group; slot 0 of the
-    trajectory takes the reset observation and done = 0; ONE step key is shared by every group.  Returns the set-up key."""
-    if group < 0 or group + len(groups) > n_groups:   # (a short key table would send the env-reset kernel out of bounds)
-        raise ValueError(f"setup: this learner holds {len(groups)} env group(s) starting at group {group}, but the job has n_groups={n_groups}")
-    allk, setup_key, step_key = split_setup_keys(L, dev, st, key, n_groups * N + 1)
-    for gi, g in enumerate(groups):
-        env_keys = allk[1 + (group + gi) * N: 1 + (group + gi + 1) * N].contiguous()
-        g.env.reset(env_keys, g.traj["obs"][0], g.traj["step_count"][0], None if g.traj["mask"] is None else g.traj["mask"][0])
-        g.traj["done"][0].zero_()
-        g.key = step_key.copy()
-    return setup_key
-
-
-def jax_permutation(L, dev, st, key: np.ndarray, n: int) -> torch.Tensor:
-    """jax.random.permutation(key, n) on the device: rounds of a stable sort by 32 random bits."""
-    rounds = int(math.ceil(3 * math.log(max(1, n)) / math.log(2 ** 32 - 1)))
-    x = torch.arange(n, dtype=torch.int32, device=dev)
-    bits = torch.empty(n, dtype=torch.int32, device=dev)
-    for _ in range(rounds):
-        ks = host_split(key, 2)
-        key, sub = ks[0], ks[1]
-        kd = torch.from_numpy(sub.view(np.int32).copy()).to(dev)
-        L.call("magpo_threefry_random_bits", kd, bits, n, st)
-        order = torch.sort(bits.to(torch.int64) & 0xFFFFFFFF, stable=True).indices
-        x = x[order]
-    return x.contiguous()
-
-
-class AdvStats:
-    """The [mean, 1 / (std + eps)] pair a loss kernel normalises the advantages of a minibatch with (rec_magpo.py:283,356; rec_sable.py:199;
-    rec_mappo.py:193), per group when several groups train as one batch of sequences.  Owns its small device buffers."""
-
-    def __init__(self, L, dev):
-        self.L, self.dev = L, dev
-        self.one = torch.zeros(2, dtype=torch.float32, device=dev)
-        self.per_group = None
-        self.ident = None
-
-    def __call__(self, m, U: int, adv_stats: Optional[torch.Tensor], ws64: torch.Tensor, st) -> torch.Tensor:
-        R = m["R"]
-        R1 = R // U
-        if U == 1:
-            if adv_stats is None:
-                self.L.call("magpo_adv_moments", m["adv"], R, ws64, self.one, st)
-            return self.one if adv_stats is None else adv_stats[0]
-        # per-group statistics, applied in place with the loss kernel's own expression (adv - mean) * rstd; identity stats after
-        if self.per_group is None or self.per_group.shape[0] != U:
-            self.per_group = torch.zeros(U, 2, device=self.dev)
-            self.ident = torch.tensor([0.0, 1.0], device=self.dev)
-        su = self.per_group if adv_stats is None else adv_stats
-        if adv_stats is None:
-            for u in range(U):
-                self.L.call("magpo_adv_moments", m["adv"][u * R1:(u + 1) * R1], R1, ws64, su[u], st)
-        a2 = m["adv"].view(U, R1)
-        a2.sub_(su[:, 0:1]).mul_(su[:, 1:2])
-        return self.ident
-
-
-class EnvGroup:
-    """Per-group rollout state: envs, trajectory, retention / GRU states, PRNG key.  A group is the
-    reference's (device, update-batch) replica (rec_magpo.py:519, :648-653); all groups of a process share
-    the parameters and the training workspaces."""
+class EnvGroup(Group):
+    """A group of the MAGPO / Sable learner: anakin.Group + retention / GRU states; its key table holds the A sample keys of every step."""
 
     def __init__(self, env_cfg, N: int, T: int, device, n_block: int = 1, n_tile: int = 1, policy: bool = True):
-        A, F = env_cfg.num_agents, obs_row_stride(env_cfg.obs_dim)
+        super().__init__(env_cfg, N, T, device, key_shape=(env_cfg.num_agents,))
         f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=device)
-        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
-        u8 = lambda *s: torch.zeros(*s, dtype=torch.uint8, device=device)
-        self.env = make_env_batch(env_cfg, N, device)
-        self.traj = dict(obs=f32(T + 1, N, A, F), step_count=i32(T + 1, N), done=u8(T + 1, N), action=i32(T, N, A), value=f32(T, N, A),
-                         reward=f32(T, N, A), log_prob=f32(T, N, A), adv=f32(T, N, A), targets=f32(T, N, A))
-        # action masks (Observation.action_mask) only for envs that have illegal actions; None = every action legal
-        self.traj["mask"] = u8(T + 1, N, A, env_cfg.num_actions) if env_cfg.has_mask else None
-        self.metrics = dict(episode_return=f32(T, N), episode_length=i32(T, N), is_terminal_step=u8(T, N))
         # (encoder, decoder self, decoder cross) retention states as 64 x 64 tiles: one (zero-padded) tile per head, or the four blocks of
         # the one 128-wide head (SableGuider.ntile)
         self.sable_hs = tuple(f32(n_block, n_tile, N, 64, 64) for _ in range(3))
-        self.prev_sable_hs = tuple(f32(n_block, n_tile, N, 64, 64) for _ in range(3))
-        # GRU actor hidden states (double-buffered) and their rollout-start copy; a guider-only system has none
-        self.policy_h = [f32(N * A, 128), f32(N * A, 128)] if policy else None
-        self.policy_h0 = f32(N * A, 128) if policy else None
-        self.last_val = f32(N, A)
-        self.key = prng_key(0)
-        self.cur = 0
-        self.skeys_host = np.zeros((T, A, 2), np.uint32)
-        self.skeys_dev = torch.zeros(T, A, 2, dtype=torch.int32, device=device)
-        self.graph = None
-        self.graph_failed = False
+        # GRU actor hidden states (double-buffered); a guider-only system has none
+        self.policy_h = [f32(N * env_cfg.num_agents, 128) for _ in range(2)] if policy else None
+        self.prev_sable_hs = self.policy_h0 = None   # rollout-start copies: views of the learner's stacked start states
+        self.skeys_host, self.skeys_dev = self.keys_host, self.keys_dev   # the tables under the names of what they hold
 
 
-class MagpoLearner:
+class MagpoLearner(AnakinLearner):
     # What a guider-only system (sable_learner.SableLearner) turns off: the GRU actor with its hidden states, carry, training pass and
     # optimiser.  Everything else -- env groups, rollout body, HIP-graph capture, gather, shuffles, micro-batches, update loop -- is shared.
     has_actor = True
@@ -172,19 +65,10 @@ class MagpoLearner:
         (rec_magpo.py:99-100): the callables the loop CALLS for acting, the two training forwards and the two optimiser steps --
         by default the bound methods of the objects above; get_learner_fn passes on what it was given (thin adaptors included).
         ``actor_torso`` = (pre, post) TorsoSpecs of the actor the learner builds itself (None: the default [128] relu torso)."""
-        from .tuning import Tuning
+        super().__init__(env_cfg, num_envs, sys, device)
         self.tuning = tuning if tuning is not None else (guider.tuning if guider is not None else Tuning.from_env())   # ONE object shared by both networks (tuning.py)
-        self.env_cfg, self.N, self.sys, self.dev = env_cfg, num_envs, sys, device
-        A, K = env_cfg.num_agents, env_cfg.num_actions
-        F, self.obs_off = net_obs(env_cfg)   # what the networks read: the whole row with the AgentIDWrapper's one-hot id, or the part behind it
-        self.A, self.K, self.F, self.T = A, K, F, sys.rollout_length
-        self.Fld = obs_row_stride(env_cfg.obs_dim)   # floats between rows as the env kernels write them
-        if num_envs % sys.num_minibatches:
-            raise ValueError("num_envs must be divisible by num_minibatches")
-        self.L = lib()
+        A, K, F = self.A, self.K, self.F
         # one contiguous buffer [guider grads | actor grads | loss scalars] = one all-reduce message (rec_magpo.py:395-409)
-        from .optim import ClipAdam
-        from .params import FlatParams, actor_layout, guider_layout
         if guider is not None:
             n_block, n_head, embed_dim = guider.nb, guider.nh, guider.EL
         self.nb, self.nh = int(n_block), int(n_head)
@@ -231,16 +115,8 @@ class MagpoLearner:
             g.prev_sable_hs = tuple(t[:, :, gi * N_:(gi + 1) * N_] for t in self._prev_hs)
             if self.has_actor:
                 g.policy_h0 = self._policy_h0[gi * N_ * A:(gi + 1) * N_ * A]
-        f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=device)
-        # optimiser state (optax adam: count, mu, nu) lives in the two ClipAdam objects: g_mu / g_nu / g_count ... below are views of it
-        self.ws64 = torch.zeros(8 * 1024, dtype=torch.float64, device=device)
-        self.gnorm = f32(2)
-        self._adv = AdvStats(self.L, device)
-        self.adv_stats = self._adv.one
-        self._mb: Dict[str, torch.Tensor] = {}
         # First-layer class tables (csrc/classtab.hip): a wrapped CoordSum token is one of A*maxval*npos distinct inputs, so the
         # layers in front of the GRU / of the first retention run on the distinct rows only.  MAGPO_CLASS_TABLES=0 = dense path.
-        import os
         # (the tables are read in place by the 64-wide fused kernels: a 128-wide net takes the dense first layers)
         # (... and need the one-hot id in the network input: the class rows are [id | target])
         self.class_tables = env_cfg.class_tables and os.environ.get("MAGPO_CLASS_TABLES", "1") != "0" and int(embed_dim) <= 64 and self.obs_off == 0
@@ -249,53 +125,30 @@ class MagpoLearner:
         self.overlap_actor = False  # opt-in (bench.py --overlap): ~3 %, but per-kernel timings then include contention
         self._actor_stream = torch.cuda.Stream(device=device) if torch.device(device).type == "cuda" else None
 
+    # the optimiser state (optax adam: count, mu, nu) lives in the two ClipAdam objects; the parity tests read it under these names
     g_mu = property(lambda self: self.g_opt.mu)
     g_nu = property(lambda self: self.g_opt.nu)
     a_mu = property(lambda self: self.a_opt.mu)
     a_nu = property(lambda self: self.a_opt.nu)
-    g_count = property(lambda self: self.g_opt.count, lambda self, v: setattr(self.g_opt, "count", int(v)))
-    a_count = property(lambda self: self.a_opt.count, lambda self, v: setattr(self.a_opt, "count", int(v)))
+    g_count = property(lambda self: self.g_opt.count)
 
-    # group-0 shortcuts (single-group callers and the parity tests)
-    env = property(lambda self: self.groups[0].env)
-    traj = property(lambda self: self.groups[0].traj)
-    metrics = property(lambda self: self.groups[0].metrics)
+    # more group-0 shortcuts (AnakinLearner has env, traj, metrics and key)
     sable_hs = property(lambda self: self.groups[0].sable_hs)
     policy_h = property(lambda self: self.groups[0].policy_h)
     last_val = property(lambda self: self.groups[0].last_val)
     _cur = property(lambda self: self.groups[0].cur)
 
-    @property
-    def key(self):
-        return self.groups[0].key
-
-    def _st(self):
-        return torch.cuda.current_stream().cuda_stream
-
-    def _net_view(self, obs: torch.Tensor) -> torch.Tensor:
-        """The part of the observation rows the networks read (net_obs): same rows, same stride, pointer behind the one-hot id."""
-        return obs if self.obs_off == 0 else obs[..., self.obs_off:]
-
-    # ------------------------------------------------------------------ setup (rec_magpo.py:642-660)
-    def setup(self, key: np.ndarray, n_groups: int = 1, group: int = 0):
-        """``n_groups`` = total number of groups in the job (ranks x local groups), ``group`` = global index of
-        this process's first group.  Reset keys are rows 1.. of split(key, n_groups*N + 1) laid out row-major
-        over (group, env); ONE step key is shared by every group (rec_magpo.py:660-671)."""
-        N = self.N
-        self.setup_key = setup_env_groups(self.L, self.dev, self._st(), self.groups, key, N, n_groups, group)
-        for g in self.groups:
-            for h in g.sable_hs:
-                h.zero_()
-            if self.has_actor:
-                g.policy_h[0].zero_()
-            g.cur = 0
+    def _reset_states(self, g: EnvGroup):
+        for h in g.sable_hs:
+            h.zero_()
+        if self.has_actor:
+            g.policy_h[0].zero_()
+        g.cur = 0
 
     # ------------------------------------------------------------------ rollout (rec_magpo.py:126-212)
     overlap_actor_step = False  # (measured slower: the acting kernel already fills every wave slot) actor hidden-state carry on a side stream beside the guider's acting kernel
     batched_actor_carry = True  # actor hidden-state carry as ONE scan over the finished trajectory (not T single steps)
     fused_act = True  # one launch per env step for the whole Sable acting step (csrc/act_fused_kernel.hpp)
-    use_graph = True  # replay the whole rollout as one HIP graph (removes ~11K host launches per rollout)
-    batch_groups = True  # update_batch_size > 1: the minibatches of all local groups train as one batch of sequences
 
     def rollout(self):
         if len(self.groups) > 1 and self.use_graph and self.fused_act and self.A <= 8 and self.class_tables and self.batched_actor_carry \
@@ -314,19 +167,7 @@ class MagpoLearner:
             for gi in range(len(self.groups)):
                 main.wait_stream(self._group_stream(gi))
             return
-        for g in self.groups:
-            self._rollout_keys(g)
-            if not self.use_graph or g.graph_failed:
-                self._rollout_body(g, g.skeys_host)            # eager: keys by value
-            elif g.graph is not None:
-                self._upload_keys(g)
-                g.graph.replay()
-            elif not getattr(g, "warmed", False):
-                self._rollout_body(g, g.skeys_host)            # first call allocates every workspace eagerly
-                g.warmed = True
-            else:
-                self._upload_keys(g)
-                self._capture(g)
+        super().rollout()
 
     def _group_stream(self, gi: int):
         if not hasattr(self, "_gstreams"):
@@ -334,26 +175,6 @@ class MagpoLearner:
         if gi not in self._gstreams:
             self._gstreams[gi] = torch.cuda.Stream(device=self.dev)
         return self._gstreams[gi]
-
-    def _upload_keys(self, g: EnvGroup):
-        # pageable source: the runtime stages the 8 KB immediately, so the host table can be reused right away
-        g.skeys_dev.copy_(torch.from_numpy(g.skeys_host.view(np.int32).copy()))
-
-    def _capture(self, g: EnvGroup):
-        cur0 = g.cur
-        try:
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                self._rollout_body(g, g.skeys_dev)
-            g.graph = graph
-            graph.replay()
-        except Exception as e:  # capture is an optimisation: never let it change results
-            import warnings
-            warnings.warn(f"HIP graph capture of the rollout failed ({e!r}); running eagerly")
-            g.graph, g.graph_failed, g.cur = None, True, cur0
-            torch.cuda.synchronize()
-            self._rollout_body(g, g.skeys_host)
 
     def _rollout_keys(self, g: EnvGroup):
         """Host key chain of one rollout (pure function of the carried key): key, policy_key = split(key) per env
@@ -434,44 +255,12 @@ class MagpoLearner:
         L.call("magpo_gae", tr["reward"], tr["value"], tr["done"], g.last_val, tr["done"][T], tr["adv"], tr["targets"], T, N, A,
                self.sys.gamma, self.sys.gae_lambda, st)
 
-    def _carry_over(self):
-        """Slot T of the trajectory becomes slot 0 of the next rollout."""
-        for g in self.groups:
-            tr = g.traj
-            tr["obs"][0].copy_(tr["obs"][self.T]); tr["step_count"][0].copy_(tr["step_count"][self.T]); tr["done"][0].copy_(tr["done"][self.T])
-            if tr["mask"] is not None:
-                tr["mask"][0].copy_(tr["mask"][self.T])
-
-    # ------------------------------------------------------------------ shuffles (jax.random.permutation)
-    def _permutation(self, key: np.ndarray, n: int) -> torch.Tensor:
-        return jax_permutation(self.L, self.dev, self._st(), key, n)
-
     # ------------------------------------------------------------------ one minibatch (rec_magpo.py:217-435)
-    def _gather(self, groups: List[int], env_idx: torch.Tensor, agent_perm: torch.Tensor):
-        """Minibatch rows (j, t, a') of the listed groups, group after group, in sequence-major order."""
-        T, N, A, F, K = self.T, self.N, self.A, self.Fld, self.K   # (observation rows are copied with their padding)
-        mb, U = env_idx.numel(), len(groups)
-        R1 = mb * T * A
-        R = U * R1
-        m = self._mb
-        if m.get("R") != R:
-            f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.dev)
-            i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=self.dev)
-            m.update(R=R, obs=f32(R, F), action=i32(R), prev=i32(R), pos=i32(R), done=torch.empty(U * mb, T, dtype=torch.uint8, device=self.dev),
-                     value=f32(R), logp=f32(R), adv=f32(R), targets=f32(R), h0idx=i32(U * mb * A) if self.has_actor else None,
-                     dg=f32(R, 64), da=f32(R, 64) if self.has_actor else None, dv=f32(R),
-                     mask=torch.empty(R, K, dtype=torch.uint8, device=self.dev) if self.env_cfg.has_mask else None)
-        for u, gi in enumerate(groups):
-            tr = self.groups[gi].traj
-            r = slice(u * R1, (u + 1) * R1)
-            h0 = m["h0idx"][u * mb * A:(u + 1) * mb * A] if self.has_actor else None   # start-state rows of the GRU actor
-            self.L.call("magpo_gather_minibatch", tr["obs"], tr["action"], tr["step_count"], tr["done"], tr["mask"], tr["value"], tr["log_prob"],
-                        tr["adv"], tr["targets"], env_idx, agent_perm, m["obs"][r], m["action"][r], m["prev"][r], m["pos"][r],
-                        m["done"][u * mb:(u + 1) * mb], None if m["mask"] is None else m["mask"][r], m["value"][r], m["logp"][r], m["adv"][r], m["targets"][r], h0, T, N, A, F, K, mb,
-                        self._st())
-            if gi and h0 is not None:
-                h0.add_(gi * N * A)      # rows of the stacked start states
-        return m
+    def _mb_buffers(self, R: int, nseq: int):
+        """Loss gradients of the guider's logits, the actor's logits and the values; the start-state rows of the GRU actor."""
+        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.dev)
+        return dict(dg=f32(R, 64), da=f32(R, 64) if self.has_actor else None, dv=f32(R),
+                    h0idx=torch.empty(nseq * self.A, dtype=torch.int32, device=self.dev) if self.has_actor else None)
 
     def _class_rows(self):
         """Distinct first-layer inputs of wrapped CoordSum tokens, in class order (built once)."""
@@ -592,7 +381,6 @@ class MagpoLearner:
         s, N, A = self.sys, self.N, self.A
         M = s.num_minibatches
         mbs = N // M
-        U = len(self.groups)
         losses = torch.zeros(s.ppo_epochs, M, self.n_loss, device=self.dev)
         # Quirk B19 (rec_magpo.py:437,447,471): the reference shuffles prev_hstates by batch_perm and carries the SHUFFLED
         # arrays into the next epoch, so epoch e reads state row hs_idx_e[i] = hs_idx_{e-1}[batch_perm_e[i]] for
@@ -630,28 +418,5 @@ class MagpoLearner:
                 ke = host_split(ke, 2)[0]  # key, entropy_key = split(key): unused for discrete actions (:373)
                 idx = batch_perm[mi * mbs:(mi + 1) * mbs].contiguous()
                 hidx = hs_idx[mi * mbs:(mi + 1) * mbs].contiguous()
-                if U == 1:
-                    grads(idx, 0, hidx)
-                    scale = 1.0
-                elif self.batch_groups:   # all local groups as one batch of sequences: the row mean IS the pmean over "batch"
-                    grads(idx, list(range(U)), hidx)
-                    scale = 1.0
-                else:  # group by group: accumulate, the 1/U goes into grad_scale
-                    self.grad_acc.zero_()
-                    for gi in range(U):
-                        grads(idx, gi, hidx)
-                        self.grad_acc.add_(self.grad_all)
-                    self.grad_all.copy_(self.grad_acc)
-                    scale = 1.0 / U
-                scale *= grad_sync(self) if grad_sync is not None else 1.0
-                self.apply_grads(scale)
-                losses[e, mi].copy_(self.loss_out)
-                losses[e, mi].mul_(scale)
-        return losses
-
-    def update_step(self, grad_sync=None):
-        """One ``_update_step`` (rec_magpo.py:106-499): rollout + GAE + training."""
-        self.rollout()
-        losses = self.update(grad_sync)
-        self._carry_over()
+                self._optimise(lambda group: grads(idx, group, hidx), grad_sync, losses[e, mi])
         return losses

@@ -22,15 +22,14 @@ from __future__ import annotations
 import dataclasses
 from typing import Callable, List, Optional
 
-import numpy as np
 import torch
 
-from ._lib import lib
 from .actor import GruActor
+from .anakin import AnakinLearner, Group, SystemConfig
 from .critic import GruCritic, global_state_ld, step_pair
-from .envs import host_split, make_env_batch, net_obs, obs_row_stride, prng_key
-from .learner import AdvStats, SystemConfig, jax_permutation, setup_env_groups
+from .envs import host_split
 from .optim import ClipAdam
+from .tuning import Tuning
 
 LOSS_NAMES = ("total_loss", "value_loss", "actor_loss", "entropy")   # the reference's loss_info keys (rec_mappo.py:286-291)
 
@@ -50,33 +49,22 @@ def raw_features(env_cfg) -> int:
     return int(env_cfg.obs_dim) - int(env_cfg.num_agents)
 
 
-class PpoGroup:
-    """Rollout state of one (device, update-batch) replica: envs, trajectory, both hidden states, PRNG key."""
+class PpoGroup(Group):
+    """A group of the PPO learner: anakin.Group + both hidden states; its key table holds the policy_key of every env step."""
 
     def __init__(self, env_cfg, N: int, T: int, device):
-        A, F = env_cfg.num_agents, obs_row_stride(env_cfg.obs_dim)
+        super().__init__(env_cfg, N, T, device, key_shape=())
         f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=device)
-        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
-        u8 = lambda *s: torch.zeros(*s, dtype=torch.uint8, device=device)
-        self.env = make_env_batch(env_cfg, N, device)
-        self.traj = dict(obs=f32(T + 1, N, A, F), step_count=i32(T + 1, N), done=u8(T + 1, N), action=i32(T, N, A), value=f32(T, N, A),
-                         reward=f32(T, N, A), log_prob=f32(T, N, A), adv=f32(T, N, A), targets=f32(T, N, A))
-        self.traj["mask"] = u8(T + 1, N, A, env_cfg.num_actions) if env_cfg.has_mask else None
-        self.metrics = dict(episode_return=f32(T, N), episode_length=i32(T, N), is_terminal_step=u8(T, N))
-        self.policy_h = [f32(N * A, 128), f32(N * A, 128)]     # double-buffered; [0] holds the carried state between rollouts
-        self.critic_h = [f32(N * A, 128), f32(N * A, 128)]
+        self.policy_h = [f32(N * env_cfg.num_agents, 128) for _ in range(2)]   # double-buffered; [0] holds the carried state between rollouts
+        self.critic_h = [f32(N * env_cfg.num_agents, 128) for _ in range(2)]
         self.policy_h0 = self.critic_h0 = None                 # views of the learner's stacked start states
-        self.last_val = f32(N, A)
-        self.key = prng_key(0)
-        self.pkeys_host = np.zeros((T, 2), np.uint32)          # policy_key of every env step
-        self.pkeys_dev = torch.zeros(T, 2, dtype=torch.int32, device=device)
-        self.graph, self.graph_failed, self.warmed = None, False, False
 
 
-class PpoLearner:
+class PpoLearner(AnakinLearner):
+    """The groups' rollouts are never replayed side by side as MagpoLearner.rollout does: the acting step's workspaces inside the two
+    networks and ``_gs_step`` are shared by all groups, so AnakinLearner.rollout's order, one group after the other on one stream, is
+    what keeps them apart."""
     n_loss = 4
-    use_graph = True      # replay the whole rollout as one HIP graph
-    batch_groups = True   # update_batch_size > 1: the minibatches of all local groups train as one batch of sequences
 
     def __init__(self, env_cfg, num_envs: int, sys: SystemConfig, device, *, centralised: bool, critic_lr: Optional[float] = None,
                  net_seed: Optional[int] = 0, wgrad_groups: int = 512, num_groups: int = 1, tuning=None, actor: Optional[GruActor] = None,
@@ -87,19 +75,12 @@ class PpoLearner:
         own from ``net_seed`` and the torso specs.  ``apply_fns`` = (actor_apply_fn, critic_apply_fn), ``update_fns`` =
         (actor_update_fn, critic_update_fn) (rec_mappo.py:67-68): the callables the minibatch CALLS for the two training forwards and the
         two optimiser steps -- by default the bound methods of the objects above."""
-        from .tuning import Tuning
+        super().__init__(env_cfg, num_envs, sys, device)
         self.tuning = tuning if tuning is not None else (actor.tuning if actor is not None else Tuning.from_env())
-        self.env_cfg, self.N, self.sys, self.dev = env_cfg, num_envs, sys, device
-        A, K = env_cfg.num_agents, env_cfg.num_actions
-        F, self.obs_off = net_obs(env_cfg)
-        self.A, self.K, self.F, self.T = A, K, F, sys.rollout_length
-        self.Fld = obs_row_stride(env_cfg.obs_dim)
+        A, K, F = self.A, self.K, self.F
         self.centralised = bool(centralised)
-        if num_envs % sys.num_minibatches:
-            raise ValueError("num_envs must be divisible by num_minibatches")
         if int(getattr(sys, "micro_batches", 1) or 1) != 1:
             raise NotImplementedError("system.micro_batches is not supported by rec_ippo / rec_mappo")
-        self.L = lib()
         # what the critic reads: agents_view rows, or global-state rows of num_agents * raw features (zero-padded to gs_ld)
         self.F_raw = raw_features(env_cfg)
         if self.centralised:
@@ -139,24 +120,8 @@ class PpoLearner:
         for gi, g in enumerate(self.groups):
             g.policy_h0 = self._policy_h0[gi * N_ * A:(gi + 1) * N_ * A]
             g.critic_h0 = self._critic_h0[gi * N_ * A:(gi + 1) * N_ * A]
-        self.ws64 = torch.zeros(8 * 1024, dtype=torch.float64, device=device)
-        self.gnorm = torch.zeros(2, device=device)
-        self._adv = AdvStats(self.L, device)   # per-minibatch, per-group advantage statistics (rec_mappo.py:193)
         self._ident_perm = torch.arange(A, dtype=torch.int32, device=device)   # PPO does not permute agents
         self._gs_step = torch.zeros(num_envs, A, self.gs_ld, device=device) if self.centralised else None
-        self._mb = {}
-
-    # group-0 shortcuts (single-group callers and the parity tests)
-    env = property(lambda self: self.groups[0].env)
-    traj = property(lambda self: self.groups[0].traj)
-    metrics = property(lambda self: self.groups[0].metrics)
-    key = property(lambda self: self.groups[0].key)
-
-    def _st(self):
-        return torch.cuda.current_stream().cuda_stream
-
-    def _net_view(self, obs: torch.Tensor) -> torch.Tensor:
-        return obs if self.obs_off == 0 else obs[..., self.obs_off:]
 
     def _critic_rows(self, obs_rows: torch.Tensor, n_env: int, out: Optional[torch.Tensor]) -> torch.Tensor:
         """The critic's input rows for ``n_env`` x A stored observation rows: the rows themselves, or their global state in ``out``."""
@@ -165,14 +130,10 @@ class PpoLearner:
         self.L.call("magpo_global_state", obs_rows, self.Fld, self.A, self.F_raw, out, self.gs_ld, n_env, self.A, self._st())
         return out
 
-    # ------------------------------------------------------------------ setup (rec_mappo.py:494-534)
-    def setup(self, key: np.ndarray, n_groups: int = 1, group: int = 0):
-        """Reset keys and the one shared step key, split as in every system here (rec_mappo.py:495-513; learner.setup_env_groups); both
-        hidden states start at zero (ScannedRNN.initialize_carry, :455-460)."""
-        self.setup_key = setup_env_groups(self.L, self.dev, self._st(), self.groups, key, self.N, n_groups, group)
-        for g in self.groups:
-            g.policy_h[0].zero_()
-            g.critic_h[0].zero_()
+    def _reset_states(self, g: PpoGroup):
+        """Both hidden states start at zero (ScannedRNN.initialize_carry, rec_mappo.py:455-460)."""
+        g.policy_h[0].zero_()
+        g.critic_h[0].zero_()
 
     # ------------------------------------------------------------------ rollout (rec_mappo.py:92-166)
     def _rollout_keys(self, g: PpoGroup):
@@ -180,56 +141,23 @@ class PpoLearner:
         key = g.key
         for t in range(self.T):
             ks = host_split(key, 2)
-            key, g.pkeys_host[t] = ks[0], ks[1]
+            key, g.keys_host[t] = ks[0], ks[1]
         g.key = key
 
-    def _upload_keys(self, g: PpoGroup):
-        g.pkeys_dev.copy_(torch.from_numpy(g.pkeys_host.view(np.int32).copy()))
-
-    def rollout(self):
-        for g in self.groups:
-            self._rollout_keys(g)
-            if not self.use_graph or g.graph_failed:
-                self._rollout_body(g, None)                     # eager: keys by value
-            elif g.graph is not None:
-                self._upload_keys(g)
-                g.graph.replay()
-            elif not g.warmed:
-                self._rollout_body(g, None)                     # first call allocates every workspace eagerly
-                g.warmed = True
-            else:
-                self._upload_keys(g)
-                self._capture(g)
-
-    def _capture(self, g: PpoGroup):
-        try:
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                self._rollout_body(g, g.pkeys_dev)
-            g.graph = graph
-            graph.replay()
-        except Exception as e:  # capture is an optimisation: never let it change results
-            import warnings
-            warnings.warn(f"HIP graph capture of the rollout failed ({e!r}); running eagerly")
-            g.graph, g.graph_failed = None, True
-            torch.cuda.synchronize()
-            self._rollout_body(g, None)
-
-    def _rollout_body(self, g: PpoGroup, pkeys_dev):
+    def _rollout_body(self, g: PpoGroup, pkeys):
         """T acting steps, the bootstrap value and GAE, all on the current stream (no parallel branches in the captured graph).  The
         carried hidden states are in policy_h[0] / critic_h[0] before and after (T is even or odd: the last state is copied back)."""
         L, st, T, N, A = self.L, self._st(), self.T, self.N, self.A
         tr = g.traj
         g.policy_h0.copy_(g.policy_h[0])
         g.critic_h0.copy_(g.critic_h[0])
-        cur = 0
+        cur, on_dev = 0, torch.is_tensor(pkeys)
         for t in range(T):
             obs_a = self._net_view(tr["obs"][t])
             obs_c = self._critic_rows(tr["obs"][t], N, self._gs_step)
             mk = None if tr["mask"] is None else tr["mask"][t]
             step_pair(self.actor, self.critic, obs_a, obs_c, tr["done"][t], g.policy_h[cur], g.policy_h[1 - cur], g.critic_h[cur], g.critic_h[1 - cur],
-                      key=None if pkeys_dev is not None else g.pkeys_host[t], key_dev=None if pkeys_dev is None else pkeys_dev[t], mask=mk,
+                      key=None if on_dev else pkeys[t], key_dev=pkeys[t] if on_dev else None, mask=mk,
                       action=tr["action"][t], log_prob=tr["log_prob"][t], value=tr["value"][t])
             cur = 1 - cur
             g.env.step(tr["action"][t], tr["reward"][t], tr["done"][t + 1], tr["obs"][t + 1], tr["step_count"][t + 1],
@@ -244,43 +172,12 @@ class PpoLearner:
         L.call("magpo_gae", tr["reward"], tr["value"], tr["done"], g.last_val, tr["done"][T], tr["adv"], tr["targets"], T, N, A,
                self.sys.gamma, self.sys.gae_lambda, st)
 
-    def _carry_over(self):
-        """Slot T of the trajectory becomes slot 0 of the next rollout."""
-        for g in self.groups:
-            tr = g.traj
-            tr["obs"][0].copy_(tr["obs"][self.T]); tr["step_count"][0].copy_(tr["step_count"][self.T]); tr["done"][0].copy_(tr["done"][self.T])
-            if tr["mask"] is not None:
-                tr["mask"][0].copy_(tr["mask"][self.T])
-
-    def _permutation(self, key: np.ndarray, n: int) -> torch.Tensor:
-        return jax_permutation(self.L, self.dev, self._st(), key, n)
-
     # ------------------------------------------------------------------ one minibatch (rec_mappo.py:171-293)
-    def _gather(self, groups: List[int], env_idx: torch.Tensor):
-        """Minibatch rows (j, t, a) of the listed groups, group after group, in sequence-major order."""
-        T, N, A, F, K = self.T, self.N, self.A, self.Fld, self.K
-        mb, U = env_idx.numel(), len(groups)
-        R1 = mb * T * A
-        R = U * R1
-        m = self._mb
-        if m.get("R") != R:
-            f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.dev)
-            i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=self.dev)
-            m.update(R=R, obs=f32(R, F), action=i32(R), prev=i32(R), pos=i32(R), done=torch.empty(U * mb, T, dtype=torch.uint8, device=self.dev),
-                     value=f32(R), logp=f32(R), adv=f32(R), targets=f32(R), h0idx=i32(U * mb * A), da=f32(R, 64), dv=f32(R),
-                     mask=torch.empty(R, K, dtype=torch.uint8, device=self.dev) if self.env_cfg.has_mask else None,
-                     gs=f32(R, self.gs_ld) if self.centralised else None)
-        for u, gi in enumerate(groups):
-            tr = self.groups[gi].traj
-            r = slice(u * R1, (u + 1) * R1)
-            h0 = m["h0idx"][u * mb * A:(u + 1) * mb * A]
-            self.L.call("magpo_gather_minibatch", tr["obs"], tr["action"], tr["step_count"], tr["done"], tr["mask"], tr["value"], tr["log_prob"],
-                        tr["adv"], tr["targets"], env_idx, self._ident_perm, m["obs"][r], m["action"][r], m["prev"][r], m["pos"][r],
-                        m["done"][u * mb:(u + 1) * mb], None if m["mask"] is None else m["mask"][r], m["value"][r], m["logp"][r], m["adv"][r],
-                        m["targets"][r], h0, T, N, A, F, K, mb, self._st())
-            if gi:
-                h0.add_(gi * N * A)      # rows of the stacked start states
-        return m
+    def _mb_buffers(self, R: int, nseq: int):
+        """Loss gradients of the logits and the values, the start-state rows of both GRUs, the critic's global-state rows."""
+        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.dev)
+        return dict(da=f32(R, 64), dv=f32(R), h0idx=torch.empty(nseq * self.A, dtype=torch.int32, device=self.dev),
+                    gs=f32(R, self.gs_ld) if self.centralised else None)
 
     def minibatch_grads(self, env_idx: torch.Tensor, group=0):
         """Forward + loss + backward of both networks for one minibatch; gradients land in actor.grads / critic.grads, the loss scalars in
@@ -290,7 +187,7 @@ class PpoLearner:
         s, T, K = self.sys, self.T, self.K
         groups = [group] if isinstance(group, int) else list(group)
         U = len(groups)
-        m = self._gather(groups, env_idx)
+        m = self._gather(groups, env_idx, self._ident_perm)
         R, nseq = m["R"], U * env_idx.numel()
         logits = self.actor_apply_fn(self._net_view(m["obs"]), m["done"], self._policy_h0, m["h0idx"], nseq, T)
         value = self.critic_apply_fn(self._critic_rows(m["obs"], nseq * T, m["gs"]), m["done"], self._critic_h0, m["h0idx"], nseq, T)
@@ -314,7 +211,6 @@ class PpoLearner:
         s, N = self.sys, self.N
         M = s.num_minibatches
         mbs = N // M
-        U = len(self.groups)
         losses = torch.zeros(s.ppo_epochs, M, self.n_loss, device=self.dev)
         for e in range(s.ppo_epochs):
             ks = host_split(self.groups[0].key, 3)    # every group holds the same key => one permutation serves all groups
@@ -325,31 +221,11 @@ class PpoLearner:
             for mi in range(M):
                 ke = host_split(ke, 2)[1]  # key, entropy_key = split(key); entropy_key is what the scan carries (:235,293), unused for discrete actions
                 idx = batch_perm[mi * mbs:(mi + 1) * mbs].contiguous()
-                if U == 1:
-                    self.minibatch_grads(idx, 0)
-                    scale = 1.0
-                elif self.batch_groups:
-                    self.minibatch_grads(idx, list(range(U)))
-                    scale = 1.0
-                else:
-                    self.grad_acc.zero_()
-                    for gi in range(U):
-                        self.minibatch_grads(idx, gi)
-                        self.grad_acc.add_(self.grad_all)
-                    self.grad_all.copy_(self.grad_acc)
-                    scale = 1.0 / U
-                scale *= grad_sync(self) if grad_sync is not None else 1.0
-                self.apply_grads(scale)
-                lo = self.loss_out
-                row = losses[e, mi]
-                row[0].copy_(lo[0]); row[1].copy_(lo[3]); row[3].copy_(lo[2])
-                torch.sub(lo[1], lo[2], alpha=s.ent_coef, out=row[2])
-                row.mul_(scale)
+                self._optimise(lambda group: self.minibatch_grads(idx, group), grad_sync, losses[e, mi])
         return losses
 
-    def update_step(self, grad_sync=None):
-        """One ``_update_step`` (rec_mappo.py:70-362): rollout + GAE + training."""
-        self.rollout()
-        losses = self.update(grad_sync)
-        self._carry_over()
-        return losses
+    def _loss_row(self, row: torch.Tensor):
+        """loss_out [total, surrogate, entropy, value_loss] in the order and with the quirk ``update`` documents."""
+        lo = self.loss_out
+        row[0].copy_(lo[0]); row[1].copy_(lo[3]); row[3].copy_(lo[2])
+        torch.sub(lo[1], lo[2], alpha=self.sys.ent_coef, out=row[2])

@@ -755,3 +755,28 @@ class SableGuider(NetBase):
 
 
 SableGuider.apply = SableGuider.train_fwd   # sable_network.apply: the chunkwise training forward (its backward: train_bwd)
+
+
+# the layout of the retention states in a learner state (systems/gpo/anakin/rec_magpo.py, systems/sable/anakin/rec_sable.py)
+def sable_hstates_logical(gd: SableGuider, t: torch.Tensor) -> torch.Tensor:
+    """Device retention states [n_block, ntile, N, 64, 64] -> the reference's [n_block, n_head, N, hs, hs] head states
+    (get_init_hstates.py:20-43).  On the device a head state sits in a zero-padded 64 x 64 tile, and a narrow net (embed_dim < 64,
+    params.WidthEmbedding) keeps logical entry (i, j) at device rows m i (q / k live in the first copy) and columns m j .. m j + m - 1
+    (v is duplicated), m = 64 / embed_dim.  The one 128-wide head of embed_dim 128 / n_head 1 lives in four 64 x 64 tiles S[I][J] (tile 2 I + J)."""
+    hw, m = gd.hs, max(1, 64 // gd.EL)
+    if gd.blockwise:
+        return torch.cat([torch.cat([t[:, 0], t[:, 1]], -1), torch.cat([t[:, 2], t[:, 3]], -1)], -2).unsqueeze(1)
+    return t[..., :hw:m, :hw:m]
+
+
+def load_sable_hstates(gd: SableGuider, dst: torch.Tensor, logical: torch.Tensor) -> None:
+    """Inverse of ``sable_hstates_logical``: write the logical head states into the device tiles ``dst``."""
+    hw, m = gd.hs, max(1, 64 // gd.EL)
+    dst.zero_()
+    if gd.blockwise:   # [n_block, 1, N, 128, 128] -> tiles (I, J)
+        full = logical[:, 0]
+        for ti in range(4):
+            dst[:, ti].copy_(full[..., 64 * (ti // 2):64 * (ti // 2) + 64, 64 * (ti % 2):64 * (ti % 2) + 64])
+        return
+    for c in range(m):   # rows m i, every column copy
+        dst[..., :hw:m, c:hw:m].copy_(logical)

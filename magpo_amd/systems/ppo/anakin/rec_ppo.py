@@ -3,11 +3,11 @@
 The two reference files differ in three places only: ``centralised_critic`` of the critic network (rec_mappo.py:429), ``add_global_state``
 of the env factory (:558) and the system name (:540).  ``make_system(name, centralised)`` returns the reference's public functions for one
 of them; rec_ippo.py / rec_mappo.py bind them at module level under the reference's names.  The bodies drive the HIP kernels
-(magpo_amd.ppo_learner.PpoLearner); the experiment loop and the learner loop are the ones rec_magpo and rec_sable use.
+(magpo_amd.ppo_learner.PpoLearner); the experiment loop, the learner loop and the shared parts of the learner state are the ones every
+system uses (magpo_amd/systems/common.py).
 """
 from __future__ import annotations
 
-import copy
 import dataclasses
 import sys
 from types import SimpleNamespace
@@ -20,13 +20,13 @@ from magpo_amd import distributed as mdist
 from magpo_amd.actor import GruActor
 from magpo_amd.config import compose
 from magpo_amd.critic import GruCritic, global_state_ld
-from magpo_amd.evaluator import make_rec_eval_act_fn
 from magpo_amd.learner import SystemConfig, host_split, obs_row_stride, prng_key
 from magpo_amd.optim import ClipAdam
 from magpo_amd.ppo_learner import LOSS_NAMES, PpoLearner, check_chunk_size, raw_features
-from magpo_amd.systems.gpo.anakin.rec_magpo import _owner, _system_config, make_learner_fn, train_and_evaluate
+from magpo_amd.systems.common import (_owner, _system_config, as_dict, load_opt_state, load_rollout_state, make_learner_fn, network_torsos,
+                                      setup_learner, snapshot_opt_state, snapshot_rollout_state, start_experiment,
+                                      train_and_evaluate_gru_actor)
 from magpo_amd.systems.ppo.types import HiddenStates, OptStates, Params, RNNLearnerState
-from magpo_amd.torso import DEFAULT_TORSO, torso_from_config
 from magpo_amd.utils import make_env as environments
 
 
@@ -35,50 +35,26 @@ def system_config(config) -> SystemConfig:
     return _system_config(config, clip_gpo=SystemConfig.clip_gpo, alpha=SystemConfig.alpha)
 
 
-def network_torsos(config, which: str):
-    """(pre, post) TorsoSpecs of ``network.actor_network`` / ``network.critic_network`` (rec_mappo.py:412-417)."""
-    node = config.network.get(which)
-    if node is None:
-        return DEFAULT_TORSO, DEFAULT_TORSO
-    return (torso_from_config(node.pre_torso) if "pre_torso" in node else DEFAULT_TORSO,
-            torso_from_config(node.post_torso) if "post_torso" in node else DEFAULT_TORSO)
-
-
 def _snapshot_state(learner: PpoLearner) -> RNNLearnerState:
     """RNNLearnerState of the learner as an independent COPY (rec_mappo.py:353-361); leaves carry a leading group axis."""
     gs = learner.groups
-    opt = lambda o: dict(count=o.count, mu=o.mu.clone(), nu=o.nu.clone())
     params = Params({k: v.clone() for k, v in learner.actor.named.items()}, {k: v.clone() for k, v in learner.critic.named.items()})
-    env_state = {f: torch.stack([getattr(g.env, f) for g in gs]) for f in gs[0].env.state_fields}
-    timestep = dict(agents_view=torch.stack([g.traj["obs"][0] for g in gs]), step_count=torch.stack([g.traj["step_count"][0] for g in gs]))
-    if gs[0].traj["mask"] is not None:
-        timestep["action_mask"] = torch.stack([g.traj["mask"][0] for g in gs])
-    return RNNLearnerState(params, OptStates(opt(learner.a_opt), opt(learner.c_opt)), gs[0].key.copy(), env_state, timestep,
-                           torch.stack([g.traj["done"][0] for g in gs]),
+    return RNNLearnerState(params, OptStates(snapshot_opt_state(learner.a_opt), snapshot_opt_state(learner.c_opt)), gs[0].key.copy(),
+                           *snapshot_rollout_state(gs),
                            HiddenStates(torch.stack([g.policy_h[0] for g in gs]), torch.stack([g.critic_h[0] for g in gs])))
 
 
 def load_learner_state(learner: PpoLearner, state: RNNLearnerState) -> None:
     """Inverse of ``_snapshot_state``: write every leaf of ``state`` into the learner's (static, graph-captured) buffers."""
-    as_dict = lambda x: x if isinstance(x, dict) else x._asdict()
     params, opts, hst = as_dict(state.params), as_dict(state.opt_states), as_dict(state.hstates)
     learner.actor.load_named(params["actor_params"])
     learner.critic.load_named(params["critic_params"])
-    for o, s in ((learner.a_opt, opts["actor_opt_state"]), (learner.c_opt, opts["critic_opt_state"])):
-        o.mu.copy_(s["mu"]); o.nu.copy_(s["nu"]); o.count = int(s["count"])
-    if state.dones.shape[0] != len(learner.groups):
-        raise ValueError(f"learner state holds {state.dones.shape[0]} env groups, the learner {len(learner.groups)}")
+    load_opt_state(learner.a_opt, opts["actor_opt_state"])
+    load_opt_state(learner.c_opt, opts["critic_opt_state"])
+    load_rollout_state(learner.groups, state.key, state.env_state, state.timestep, state.dones)
     for gi, grp in enumerate(learner.groups):
-        for f in grp.env.state_fields:
-            getattr(grp.env, f).copy_(state.env_state[f][gi])
-        grp.traj["obs"][0].copy_(state.timestep["agents_view"][gi])
-        if grp.traj["mask"] is not None:
-            grp.traj["mask"][0].copy_(state.timestep["action_mask"][gi])
-        grp.traj["step_count"][0].copy_(state.timestep["step_count"][gi])
-        grp.traj["done"][0].copy_(state.dones[gi])
         grp.policy_h[0].copy_(hst["policy_hidden_state"][gi])
         grp.critic_h[0].copy_(hst["critic_hidden_state"][gi])
-        grp.key = np.array(state.key, dtype=np.uint32).copy()
 
 
 def make_system(name: str, centralised: bool) -> SimpleNamespace:
@@ -92,7 +68,7 @@ def make_system(name: str, centralised: bool) -> SimpleNamespace:
 
         Under the rule of rec_sable.get_learner_fn: the callables must be the bound methods ``GruActor.apply`` / ``GruCritic.apply`` and
         ``ClipAdam.update`` of the objects that own the device buffers (or thin functools.wraps / functools.partial adaptors around them),
-        and the loop CALLS exactly what it is given; anything else raises the ``TypeError`` of rec_magpo._owner."""
+        and the loop CALLS exactly what it is given; anything else raises the ``TypeError`` of common._owner."""
         actor_apply_fn, critic_apply_fn = apply_fns
         actor_update_fn, critic_update_fn = update_fns
         critic = _owner(critic_apply_fn, GruCritic, "apply", "apply_fns[1] (critic_apply_fn)")
@@ -119,7 +95,6 @@ def make_system(name: str, centralised: bool) -> SimpleNamespace:
             raise NotImplementedError("HIP kernels support hidden_state_dim=128")
         check_chunk_size(config.system.get("recurrent_chunk_size"), int(config.system.rollout_length))
         device = device or torch.device("cuda", torch.cuda.current_device())
-        U = int(config.system.update_batch_size)
         cfg, sysc = env.cfg, system_config(config)
         csys = dataclasses.replace(sysc, actor_lr=float(config.system.critic_lr))   # ClipAdam reads its rate as actor_lr
         obs_ld = obs_row_stride(cfg.obs_dim)
@@ -139,18 +114,11 @@ def make_system(name: str, centralised: bool) -> SimpleNamespace:
         apply_fns = (actor_network.apply, critic_network.apply)
         update_fns = (actor_optim.update, critic_optim.update)
         learn = get_learner_fn(env, apply_fns, update_fns, config)
-        learner = learn.learner
-        learner.setup(key, n_groups=world * U, group=rank * U)
-        learner._live_state = _snapshot_state(learner)
-        return learn, actor_network, learner._live_state
+        return learn, actor_network, setup_learner(learn, key, _snapshot_state, rank, world)
 
     def run_experiment(_config) -> float:
         """Runs experiment (rec_mappo.py:538-677)."""
-        _config.logger.system_name = name
-        config = copy.deepcopy(_config)
-        rank, world, local = mdist.init_from_env()
-        torch.cuda.set_device(local)
-        device = torch.device("cuda", local)
+        config, rank, world, device = start_experiment(_config, name)
         # recurrent_chunk_size (rec_mappo.py:545-555): null means the rollout length
         check_chunk_size(config.system.get("recurrent_chunk_size"), int(config.system.rollout_length))
         if config.system.get("recurrent_chunk_size") is None:
@@ -161,13 +129,7 @@ def make_system(name: str, centralised: bool) -> SimpleNamespace:
         ks = host_split(prng_key(int(config.system.seed)), 4)
         key, key_e, actor_net_key, critic_net_key = ks[0], ks[1], ks[2], ks[3]
         learn, actor_network, learner_state = learner_setup(env, (key, actor_net_key, critic_net_key), config, device, rank, world)
-
-        eval_actor = GruActor(env.num_agents, env.action_dim, env.obs_dim, device, obs_ld=obs_row_stride(env.cfg.obs_dim),
-                              pre_torso=actor_network.pre_spec, post_torso=actor_network.post_spec)
-        eval_act_fn = make_rec_eval_act_fn(eval_actor, config)
-        return train_and_evaluate(config, env, eval_env, learn, learner_state, eval_act_fn, key, key_e, device, rank, world,
-                                  init_act_state=lambda batch: {"hidden_state": torch.zeros(batch * env.num_agents, 128, device=device)},
-                                  eval_params=lambda state: state.params.actor_params)
+        return train_and_evaluate_gru_actor(config, env, eval_env, learn, actor_network, learner_state, key, key_e, device, rank, world)
 
     def hydra_entry_point(overrides: Optional[List[str]] = None) -> float:
         """Experiment entry point (rec_mappo.py:680-693): compose configs/default/<system>.yaml + CLI overrides."""

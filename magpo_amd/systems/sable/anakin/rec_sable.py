@@ -6,13 +6,12 @@ Same public names and call contract as the reference system file:
     learner_setup(env, keys, config) -> (learn, sable_execution_fn, init_learner_state)   rec_sable.py:351-478
     get_learner_fn(env, apply_fns, update_fn, config) -> LearnerFn                        rec_sable.py:53-348
 The bodies drive the HIP kernels (magpo_amd.sable_learner.SableLearner); the experiment loop, the learner loop and the state layout
-helpers are the ones rec_magpo uses.
+helpers are the ones every system uses (magpo_amd/systems/common.py, magpo_amd/sable.py).
 
     python -m magpo_amd.systems.sable.anakin.rec_sable env=coordsum env/scenario=3x30-50 arch.num_envs=64
 """
 from __future__ import annotations
 
-import copy
 import sys
 from typing import Callable, Dict, List, Optional
 
@@ -23,10 +22,10 @@ from magpo_amd import distributed as mdist
 from magpo_amd.config import compose
 from magpo_amd.learner import SystemConfig, host_split, obs_row_stride, prng_key
 from magpo_amd.optim import ClipAdam
-from magpo_amd.sable import SableGuider
+from magpo_amd.sable import SableGuider, load_sable_hstates, sable_hstates_logical
 from magpo_amd.sable_learner import LOSS_NAMES, SableLearner
-from magpo_amd.systems.gpo.anakin.rec_magpo import (_owner, _system_config, load_sable_hstates, make_learner_fn, sable_hstates_logical,
-                                                    train_and_evaluate)
+from magpo_amd.systems.common import (_owner, _system_config, as_dict, load_opt_state, load_rollout_state, make_learner_fn, setup_learner,
+                                      snapshot_opt_state, snapshot_rollout_state, start_experiment, train_and_evaluate)
 from magpo_amd.systems.sable.types import HiddenStates, LearnerState, Transition  # noqa: F401
 from magpo_amd.types import ExperimentOutput  # noqa: F401
 from magpo_amd.utils import make_env as environments
@@ -44,37 +43,22 @@ def _snapshot_state(learner: SableLearner) -> LearnerState:
     the first transition records, rec_sable.py:112)."""
     gs, gd = learner.groups, learner.guider
     params = {k: v.clone() for k, v in gd.named.items()}
-    opt = dict(count=learner.g_count, mu=learner.g_mu.clone(), nu=learner.g_nu.clone())
     hs = HiddenStates(*[torch.stack([sable_hstates_logical(gd, g.sable_hs[i]) for g in gs]) for i in range(3)])
-    env_state = {f: torch.stack([getattr(g.env, f) for g in gs]) for f in gs[0].env.state_fields}
-    timestep = dict(agents_view=torch.stack([g.traj["obs"][0] for g in gs]), step_count=torch.stack([g.traj["step_count"][0] for g in gs]),
-                    last=torch.stack([g.traj["done"][0] for g in gs]))
-    if gs[0].traj["mask"] is not None:
-        timestep["action_mask"] = torch.stack([g.traj["mask"][0] for g in gs])
-    return LearnerState(params, opt, gs[0].key.copy(), env_state, timestep, hs)
+    env_state, timestep, timestep_last = snapshot_rollout_state(gs)
+    timestep["last"] = timestep_last
+    return LearnerState(params, snapshot_opt_state(learner.g_opt), gs[0].key.copy(), env_state, timestep, hs)
 
 
 def load_learner_state(learner: SableLearner, state: LearnerState) -> None:
     """Inverse of ``_snapshot_state``: write every leaf of ``state`` into the learner's (static, graph-captured) buffers."""
-    as_dict = lambda x: x if isinstance(x, dict) else x._asdict()
     learner.guider.load_named(state.params)
-    opt = state.opt_states
-    learner.g_mu.copy_(opt["mu"]); learner.g_nu.copy_(opt["nu"]); learner.g_count = int(opt["count"])
+    load_opt_state(learner.g_opt, state.opt_states)
     hst = as_dict(state.hstates)
     sable = (hst["encoder"], hst["decoder_self_retn"], hst["decoder_cross_retn"])
-    if state.timestep["last"].shape[0] != len(learner.groups):
-        raise ValueError(f"learner state holds {state.timestep['last'].shape[0]} env groups, the learner {len(learner.groups)}")
+    load_rollout_state(learner.groups, state.key, state.env_state, state.timestep, state.timestep["last"])
     for gi, grp in enumerate(learner.groups):
-        for f in grp.env.state_fields:
-            getattr(grp.env, f).copy_(state.env_state[f][gi])
-        grp.traj["obs"][0].copy_(state.timestep["agents_view"][gi])
-        if grp.traj["mask"] is not None:
-            grp.traj["mask"][0].copy_(state.timestep["action_mask"][gi])
-        grp.traj["step_count"][0].copy_(state.timestep["step_count"][gi])
-        grp.traj["done"][0].copy_(state.timestep["last"][gi])
         for i in range(3):
             load_sable_hstates(learner.guider, grp.sable_hs[i], sable[i][gi])
-        grp.key = np.array(state.key, dtype=np.uint32).copy()
 
 
 def get_learner_fn(env, apply_fns, update_fn, config):
@@ -85,7 +69,7 @@ def get_learner_fn(env, apply_fns, update_fn, config):
 
     As in the MAGPO system the callables must be methods of the objects that own the device buffers -- ``SableGuider.get_actions``,
     ``SableGuider.apply`` and ``ClipAdam.update``, or thin ``functools.wraps`` / ``functools.partial`` adaptors around them -- and the
-    loop CALLS exactly what it is given; anything else raises the ``TypeError`` of rec_magpo._owner.  State in, state out: a state
+    loop CALLS exactly what it is given; anything else raises the ``TypeError`` of common._owner.  State in, state out: a state
     other than the last one produced is loaded into the buffers first, so ``learn`` is a function of its argument."""
     sable_action_select_fn, sable_apply_fn = apply_fns
     guider = _owner(sable_apply_fn, SableGuider, "apply", "apply_fns[1] (sable_apply_fn)")
@@ -114,7 +98,6 @@ def learner_setup(env, keys, config, device=None, rank: int = 0, world: int = 1)
     if int(nc.embed_dim) not in (16, 32, 64, 128) or int(nc.n_head) not in (1, 2, 4):
         raise NotImplementedError("HIP kernels support embed_dim in {16,32,64,128}, n_head in {1,2,4} (any n_block)")
     device = device or torch.device("cuda", torch.cuda.current_device())
-    U = int(config.system.update_batch_size)
     cfg, sysc = env.cfg, system_config(config)
     # parameters = what flax creates from net_key (rec_sable.py:403-409; magpo_amd/params.py)
     sable_network = SableGuider(cfg.num_agents, cfg.num_actions, env.obs_dim, device, obs_ld=obs_row_stride(cfg.obs_dim), embed_dim=int(nc.embed_dim),
@@ -123,10 +106,7 @@ def learner_setup(env, keys, config, device=None, rank: int = 0, world: int = 1)
     optim = ClipAdam(sable_network, sysc)
     apply_fns = (sable_network.get_actions, sable_network.apply)   # execution function, training function (rec_sable.py:413-416)
     learn = get_learner_fn(env, apply_fns, optim.update, config)
-    learner = learn.learner
-    learner.setup(key, n_groups=world * U, group=rank * U)
-    learner._live_state = _snapshot_state(learner)
-    return learn, apply_fns[0], learner._live_state
+    return learn, apply_fns[0], setup_learner(learn, key, _snapshot_state, rank, world)
 
 
 def get_init_hidden_state(sable_network: SableGuider, batch_size: int) -> torch.Tensor:
@@ -184,12 +164,7 @@ def make_rec_sable_act_fn(actor_apply_fn: Callable) -> Callable:
 
 def run_experiment(_config) -> float:
     """Runs experiment (rec_sable.py:481-620)."""
-    _config.logger.system_name = "rec_sable"
-    config = copy.deepcopy(_config)
-    rank, world, local = mdist.init_from_env()
-    torch.cuda.set_device(local)
-    device = torch.device("cuda", local)
-
+    config, rank, world, device = start_experiment(_config, "rec_sable")
     env, eval_env = environments.make(config)
     ks = host_split(prng_key(int(config.system.seed)), 3)
     key, key_e, net_key = ks[0], ks[1], ks[2]

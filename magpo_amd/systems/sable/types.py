@@ -2,7 +2,7 @@
 
 Same names and fields as the reference NamedTuples.  Leaves are device tensors with a leading group axis (the reference's update-batch
 axis); the hidden states use the logical [embed_dim / n_head, embed_dim / n_head] head-state layout of ``GPOLearnerState``
-(rec_magpo.sable_hstates_logical)."""
+(magpo_amd.sable.sable_hstates_logical)."""
 from __future__ import annotations
 
 from typing import Any, Callable, Dict, NamedTuple

@@ -236,13 +236,14 @@ def test_get_learner_fn_calls_the_functions_it_is_given_and_rejects_foreign_call
     from magpo_amd.learner import host_split, prng_key
     from magpo_amd.optim import ClipAdam
     from magpo_amd.sable import SableGuider
+    from magpo_amd.systems import common
     from magpo_amd.systems.gpo.anakin import rec_magpo
     from magpo_amd.utils import make_env as environments
     cfg = compose("rec_magpo", ["env=coordsum", "env/scenario=3x10-30", "arch.num_envs=6", "system.total_timesteps=~", "system.num_updates=2",
                                 "system.rollout_length=8", "system.ppo_epochs=2", "env.kwargs.time_limit=5"])
     cfg.system.num_updates_per_eval = 1
     env, _ = environments.make(cfg)
-    sysc = rec_magpo._system_config(cfg)
+    sysc = common._system_config(cfg)
     key = host_split(prng_key(3), 4)[0]
 
     def build(adapt):

@@ -63,7 +63,7 @@ def test_module_exports_the_reference_names():
 
 def test_system_config_reads_a_sable_config():
     from magpo_amd.config import compose
-    from magpo_amd.systems.gpo.anakin.rec_magpo import _system_config
+    from magpo_amd.systems.common import _system_config
     from magpo_amd.systems.sable.anakin.rec_sable import system_config
     cfg = compose("rec_sable", ["env=coordsum", "system.micro_batches=4", "system.ent_coef=0.001"])
     s = system_config(cfg)
