@@ -314,6 +314,22 @@ int magpo_gru_scan_bwd(const float* gates, const float* hprev, const unsigned ch
  * a D outside the set, a null pointer. */
 int magpo_gru_cell_step(const int* dims_host, const void* const* ptrs_host, int nptrs, const unsigned char* reset, int R,
                         int A, magpo_stream_t stream);
+/* ONE acting step of feed-forward PPO, for one or two networks in a single launch (csrc/mlp_step.hip; ff_mappo.py:75-100):
+ * Y = head(MLPTorso(X)) on R rows, per layer Dense -> activation (no LayerNorm), then Dense(NOUT) without activation; the hidden activations
+ * stay in LDS.  The networks of one launch may differ in everything below.
+ *   dims_host[1 + 10 nnets] = {nnets (1 or 2); per network: F, ldx, layers, width 0, width 1, width 2, activation, activate_final, NOUT, ldy}
+ *     F features per row, 1..128, rows ldx >= F floats apart (any ldx: a row need not be 16-byte aligned; columns >= F are never read);
+ *     1..3 layers, every used width 64 / 128 / 192 / 256 (unused width slots are ignored); activation 1 relu / 5 tanh as magpo_linear,
+ *     applied to every layer but the last, and to the last when activate_final is 1; NOUT 1..32, output rows ldy >= NOUT floats apart.
+ *   ptrs_host[10 nnets] (device pointers), per network: X, W0, b0, W1, b1, W2, b2, Wh, bh, Y (slots of unused layers may be null)
+ *     Wi, i > 0: [width i][width i-1], the transposed layout magpo_transpose_pad writes; Wh: [>= 32][last width] likewise (rows >= NOUT are
+ *     read, never used); bi [width i], bh [NOUT].
+ *     W0: when F <= 32, width 0 = 128 and layer 0 is followed by relu -- the first layer magpo_small_linear serves -- the NATURAL [F][128]
+ *     kernel, summed as that kernel sums it; otherwise the transposed [width 0][KP], KP = 64 for F <= 32, else 128, with zero columns >= F.
+ * Writes exactly columns 0 .. NOUT-1 of rows 0 .. R-1 of each Y (NOUT = 1, ldy = 1: a value vector).  Grid (ceil(R / 64), nnets).
+ * Rejected before any launch: R < 1, nnets not 1 or 2, nptrs != 10 nnets, layers outside 1..3, a used width outside the set, F, ldx, NOUT or
+ * ldy out of range, an unknown activation code, activate_final not 0 / 1, a null pointer in a used slot. */
+int magpo_mlp_act_step(const int* dims_host, const void* const* ptrs_host, int nptrs, int R, magpo_stream_t stream);
 /* observation.global_state of the centralised critic (mava/wrappers/matrax.py:128-131, jumanji.py:61-67): out [N A][ld], row (n, a) = the
  * concatenation over agents j of obs[(n, j)][id_cols .. id_cols + F_raw) (the raw agent views behind the id_cols leading agent-id columns of the
  * stored rows, row stride ldo), the same for every a, zero from column A F_raw to ld.  ld is 64 or 128 and A F_raw <= ld. */

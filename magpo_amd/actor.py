@@ -16,7 +16,7 @@ import contextlib
 import numpy as np
 import torch
 
-from .netbase import NetBase
+from .netbase import TorsoNet
 from .params import FlatParams, actor_layout, actor_named_views, init_actor, init_actor_from_key
 from .torso import DEFAULT_TORSO, TorsoSpec, layer_name
 from .tuning import Tuning
@@ -24,7 +24,7 @@ from .tuning import Tuning
 H = 128
 
 
-class GruActor(NetBase):
+class GruActor(TorsoNet):
     LINEAR_VARIANT = "actor_linear_variant"
 
     def __init__(self, n_agents: int, action_dim: int, obs_dim: int, device, *, hidden: int = 128, wgrad_groups: int = 512,
@@ -104,39 +104,6 @@ class GruActor(NetBase):
             L.call("magpo_copy_rows", src, 3 * H, dst[:, 2 * H:], 3 * H, rows, H, st)
             L.call("magpo_copy_rows", src[:, H:], 3 * H, dst, 3 * H, rows, 2 * H, st)
 
-    def _torso_fwd(self, prefix, spec, X, ldx, R, ctx):
-        """One MLPTorso (torsos.py:36-47) on R rows of X (stride ldx; the pre-torso's X are observation rows of F features).  Buffers are
-        named by ``ctx`` so that the rollout, the carry and the training forward keep their own.  Returns one record per layer:
-        (input, input stride, KIN, output y [R, width], (xhat, rstd) of the LayerNorm or None)."""
-        L, st, v, b = self.L, self._st(), self.v, self.b
-        recs = []
-        kin = ldx if prefix == "post" else None
-        for i, d in enumerate(spec.layer_sizes):
-            n = layer_name(prefix, i)
-            y = b.get(f"{ctx}{n}.y", (R, d))
-            Wt = self.wt.get(n)
-            if prefix == "pre" and i == 0:
-                if self.small_first:
-                    L.call("magpo_small_linear", X, ldx, self.F, v["pre.kernel"], v["pre.bias"], y, d, d, R, 1, st)
-                    recs.append((X, ldx, None, y, None))
-                    X, ldx, kin = y, d, d
-                    continue
-                if not self.wide:   # observation rows as a zero-padded [R][64] operand
-                    xp = b.get(f"{ctx}pre.xp", (R, 64))
-                    L.call("magpo_small_operand", 2, X, ldx, self.F, None, None, 0, xp, R, st)
-                    X, ldx = xp, 64
-                kin, Wt = self.KP, self.wt["pre"]
-            if spec.use_layer_norm:
-                z = b.get(f"{ctx}{n}.z", (R, d)); xh = b.get(f"{ctx}{n}.xh", (R, d)); rs = b.get(f"{ctx}{n}.rs", (R,))
-                self.lin(X, ldx, Wt, v[n + ".bias"], z, d, R, kin, d)
-                L.call("magpo_ln_act_fwd", z, d, v[n + ".ln.bias"], y, d, xh, d, rs, R, d, spec.act(i), st)
-                recs.append((X, ldx, kin, y, (xh, rs)))
-            else:
-                self.lin(X, ldx, Wt, v[n + ".bias"], y, d, R, kin, d, act=spec.act(i))
-                recs.append((X, ldx, kin, y, None))
-            X, ldx, kin = y, d, d
-        return recs
-
     def pre_torso(self, obs, obs_ld, R, ctx):
         """Pre-torso on R observation rows (stride obs_ld) -> its layer records; the output (GRU input) is recs[-1][3], [R, D_pre]."""
         return self._torso_fwd("pre", self.pre_spec, obs, obs_ld, R, ctx)
@@ -146,42 +113,6 @@ class GruActor(NetBase):
         recs = self._torso_fwd("post", self.post_spec, hs, H, R, ctx)
         self.lin(recs[-1][3], self.Dpost, self.wt["head"], self.v["head.bias"], logits, 64, R, self.Dpost, self.K)
         return recs
-
-    def _torso_bwd(self, prefix, spec, recs, dy):
-        """Backward through one torso.  ``dy`` = gradient at the last layer's output, already multiplied by that layer's activation
-        derivative when the layer has no LayerNorm (the GEMM that produced it fused the mask: act 4 / 6).  Fills the layers' parameter
-        gradients; returns the gradient at layer 0's pre-activation (the small first layer: at its output, unmasked)."""
-        L, st, gv, v, b = self.L, self._st(), self.gv, self.v, self.b
-        R = dy.shape[0]
-        for i in range(len(spec.layer_sizes) - 1, -1, -1):
-            n = layer_name(prefix, i)
-            d = spec.layer_sizes[i]
-            X, ldx, kin, y, ln = recs[i]
-            if prefix == "pre" and i == 0 and self.small_first:
-                return dy
-            if ln is not None:   # LayerNorm + activation backward on the rows; the LayerNorm bias gradient from per-workgroup slabs
-                dz = b.get(f"g_{prefix}{i}.dz", (R, d))
-                grid = L.call("magpo_row_grid", R)
-                slab = b.get(f"g_{prefix}{i}.slab", (grid, d))
-                L.call("magpo_ln_act_bwd", dy, d, y, d, ln[0], d, ln[1], dz, d, slab, R, d, spec.act(i), st)
-                self.reduce(slab, gv[n + ".ln.bias"])
-            else:
-                dz = dy
-            krows = self.F if (prefix == "pre" and i == 0) else None
-            self.wgrad(X, ldx, dz, d, R, kin, d, gv[n + ".kernel"], gv[n + ".bias"], krows=krows)
-            if i == 0:
-                return dz
-            dy = b.get(f"g_{prefix}{i - 1}.dy", (R, spec.layer_sizes[i - 1]))
-            self._dx(dz, d, v[n + ".kernel"], d, spec.layer_sizes[i - 1], R, dy, spec, i - 1, recs[i - 1])
-        return dy
-
-    def _dx(self, dsrc, ldsrc, W_nat, KIN, NOUT, R, dst, spec, j, rec):
-        """dst = dsrc W^T (W in its natural [NOUT, KIN] layout), times the activation derivative of layer j of ``spec`` when that
-        layer has no LayerNorm (fused epilogue: act 4 ReLU mask / act 6 tanh, its output as the mask argument)."""
-        act, M = 0, None
-        if rec[4] is None and spec.act(j):
-            act, M = (4 if spec.act(j) == 1 else 6), rec[3]
-        self.lin(dsrc, ldsrc, W_nat, None, dst, NOUT, R, KIN, NOUT, act=act, mask=M)
 
     def _wgrad_nrz(self, emb, dg, R, gw, dW, db):
         """dW_i, db_i from dg's columns 0..3H (gate blocks n | r | z) into W_i's order, on the weight-gradient stream."""
@@ -309,12 +240,7 @@ class GruActor(NetBase):
             self._dx(dxi, ldx, wi_t, 3 * H, Dp, R, demb, self.pre_spec, len(pre) - 1, pre[-1])
         d0 = self._torso_bwd("pre", self.pre_spec, pre, demb)
         if self.small_first:   # Dense(F->128)+ReLU weight gradient on the raw observation rows
-            emb0 = pre[0][3]
-            grid = L.call("magpo_row_grid", R)
-            sw = b.get("g_slabw", (grid, 33 * H))
-            L.call("magpo_small_relu_wgrad", obs, self.Fld, F, emb0, d0, sw, R, st)
-            self.reduce(sw, gv["pre.kernel"], P=F * H, stride=33 * H)
-            self.reduce(sw[:, 32 * H:], gv["pre.bias"], P=H, stride=33 * H)
+            self._small_first_wgrad(obs, pre[0][3], d0, R)
         self._join_wgrad()
 
 

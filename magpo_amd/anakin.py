@@ -239,10 +239,12 @@ class AnakinLearner:
         return jax_permutation(self.L, self.dev, self._st(), key, n)
 
     # ------------------------------------------------------------------ one minibatch (rec_magpo.py:441-462)
-    def _gather(self, groups: List[int], env_idx: torch.Tensor, agent_perm: torch.Tensor):
+    def _gather(self, groups: List[int], env_idx: torch.Tensor, agent_perm: torch.Tensor, shape=None):
         """Minibatch rows (j, t, a') of the listed groups, group after group, in sequence-major order.  ``h0idx`` (where the system's
-        ``_mb_buffers`` has one): the rows of the sequences' GRU start states in the start states of all groups, stacked."""
-        T, N, A, F, K = self.T, self.N, self.A, self.Fld, self.K   # (observation rows are copied with their padding)
+        ``_mb_buffers`` has one): the rows of the sequences' GRU start states in the start states of all groups, stacked.  ``shape`` =
+        (T, N) the time-major trajectory buffers are read as (default: as they are; a feed-forward learner gathers single steps, (1, T N))."""
+        T, N = (self.T, self.N) if shape is None else shape
+        A, F, K = self.A, self.Fld, self.K   # (observation rows are copied with their padding)
         mb, U = env_idx.numel(), len(groups)
         R1 = mb * T * A
         R = U * R1

@@ -70,6 +70,42 @@ def make_rec_eval_act_fn(actor_apply_fn: GruActor, config) -> Callable:
     return eval_act_fn
 
 
+def make_ff_eval_act_fn(actor_apply_fn, config) -> Callable:
+    """Makes ``EvalActFn(params, timestep, key, actor_state) -> (action, actor_state)`` for a feed-forward actor (evaluator.py:174-185).
+    ``actor_apply_fn`` is the ``FfActor`` that owns the kernels; the action is the mode of the masked categorical with
+    ``arch.evaluation_greedy``, else one sample over the whole [N, A] batch from ``key``; the actor state is ``{}`` in and out."""
+    actor = actor_apply_fn
+    greedy = bool(config.arch.evaluation_greedy)
+    L = lib()
+    loaded = {"params": None}
+
+    def eval_act_fn(params: Dict[str, torch.Tensor], timestep, key: np.ndarray, actor_state):
+        if params is not None and params is not actor.named and params is not loaded["params"]:
+            actor.load_named(params)
+            loaded["params"] = params
+        view, mask = timestep.observation.agents_view, timestep.observation.action_mask
+        N, A = view.shape[0], view.shape[1]
+        if view.stride(2) != 1 or view.stride(1) != actor.Fld or view.stride(0) != A * actor.Fld:
+            raise ValueError(f"agents_view rows must be {actor.Fld} floats apart (got strides {tuple(view.stride())})")
+        if mask is not None:
+            mask = mask.to(torch.uint8).contiguous()
+        logits = actor.logits(view)
+        action = torch.empty(N, A, dtype=torch.int32, device=view.device)
+        if greedy:   # pi.mode() of the masked categorical (heads.py:56-63: illegal logits -> finfo.min)
+            lg = logits[:, :actor.K]
+            if mask is not None:
+                lg = torch.where(mask.view(N * A, actor.K) != 0, lg, torch.full_like(lg, torch.finfo(torch.float32).min))
+            action.copy_(lg.argmax(-1).view(N, A))
+        else:
+            key = np.asarray(key, dtype=np.uint32).reshape(2)
+            logp = torch.empty(N * A, device=view.device)
+            L.call("magpo_sample_categorical", logits, 64, mask, 0 if mask is None else actor.K, int(key[0]), int(key[1]), None, action, 1,
+                   logp, 1, None, 0, None, 0, N * A, actor.K, torch.cuda.current_stream().cuda_stream)
+        return action, {}
+
+    return eval_act_fn
+
+
 def get_eval_fn(env, act_fn: Callable, config, absolute_metric: bool, device=None, n_devices: int = 1):
     """``EvalFn(params, key, init_act_state) -> metrics`` (evaluator.py:66-185) over the MarlEnv contract: ``env.reset(keys)``,
     then ``time_limit + 1`` times ``act_fn(params, timestep, act_key, actor_state)`` and ``env.step(env_state, action)``; the
@@ -95,7 +131,7 @@ def get_eval_fn(env, act_fn: Callable, config, absolute_metric: bool, device=Non
             reset_keys = torch.empty(n_envs, 2, dtype=torch.int32, device=dev)
             L.call("magpo_threefry_split", kd, reset_keys, n_envs, torch.cuda.current_stream().cuda_stream)
             env_state, ts = env.reset(reset_keys)
-            actor_state = {"hidden_state": init_act_state["hidden_state"].clone()}
+            actor_state = {k: v.clone() for k, v in init_act_state.items()}   # {"hidden_state": ...}, or {} for a feed-forward actor
             got = torch.zeros(n_envs, dtype=torch.bool, device=dev)
             ep_ret = torch.zeros(n_envs, device=dev)
             ep_len = torch.zeros(n_envs, dtype=torch.int32, device=dev)

@@ -1,5 +1,6 @@
-"""Host-side plumbing shared by the two networks (SableGuider, GruActor): named workspaces, transposed weight copies, the dense-layer
-and weight-gradient launches with the optional side stream, slab reductions and cached device-pointer tables."""
+"""Host-side plumbing shared by the networks (SableGuider, GruActor, FfActor): named workspaces, transposed weight copies, the dense-layer
+and weight-gradient launches with the optional side stream, slab reductions and cached device-pointer tables; ``TorsoNet`` adds the forward
+and backward of one MLPTorso for the networks that have one (GruActor / GruCritic, FfActor / FfCritic)."""
 from __future__ import annotations
 
 from typing import Dict, Optional
@@ -8,6 +9,7 @@ import numpy as np
 import torch
 
 from ._lib import lib
+from .torso import layer_name
 from .tuning import Tuning
 
 
@@ -102,3 +104,89 @@ class NetBase:
             tab = self._tabs[key] = np.array([0 if t is None else t.data_ptr() for t in (tensors() if callable(tensors) else tensors)],
                                              dtype=np.uint64)
         return tab
+
+
+class TorsoNet(NetBase):
+    """NetBase + the MLPTorso forward / backward (magpo_amd/torso.py) on the dense, LayerNorm and small-input kernels.  The network supplies
+    ``v`` / ``gv`` (parameter and gradient views named by ``layer_name``), ``wt`` (transposed copies kept by its ``refresh``), ``wg_ws``, and for
+    its ``pre`` torso (the one that reads observation rows) ``small_first`` and ``KP``: the first layer on narrow observations is served by the
+    small-input kernels when it is Dense(F->128)+ReLU without LayerNorm; any other first layer reads the observations as a zero-padded
+    [R][64] operand (magpo_small_operand) through magpo_linear / magpo_wgrad."""
+
+    def _torso_fwd(self, prefix, spec, X, ldx, R, ctx):
+        """One MLPTorso (torsos.py:36-47) on R rows of X (stride ldx; the pre-torso's X are observation rows of F features).  Buffers are
+        named by ``ctx`` so that the rollout, the carry and the training forward keep their own.  Returns one record per layer:
+        (input, input stride, KIN, output y [R, width], (xhat, rstd) of the LayerNorm or None)."""
+        L, st, v, b = self.L, self._st(), self.v, self.b
+        recs = []
+        kin = ldx if prefix == "post" else None
+        for i, d in enumerate(spec.layer_sizes):
+            n = layer_name(prefix, i)
+            y = b.get(f"{ctx}{n}.y", (R, d))
+            Wt = self.wt.get(n)
+            if prefix == "pre" and i == 0:
+                if self.small_first:
+                    L.call("magpo_small_linear", X, ldx, self.F, v["pre.kernel"], v["pre.bias"], y, d, d, R, 1, st)
+                    recs.append((X, ldx, None, y, None))
+                    X, ldx, kin = y, d, d
+                    continue
+                if not self.wide:   # observation rows as a zero-padded [R][64] operand
+                    xp = b.get(f"{ctx}pre.xp", (R, 64))
+                    L.call("magpo_small_operand", 2, X, ldx, self.F, None, None, 0, xp, R, st)
+                    X, ldx = xp, 64
+                kin, Wt = self.KP, self.wt["pre"]
+            if spec.use_layer_norm:
+                z = b.get(f"{ctx}{n}.z", (R, d)); xh = b.get(f"{ctx}{n}.xh", (R, d)); rs = b.get(f"{ctx}{n}.rs", (R,))
+                self.lin(X, ldx, Wt, v[n + ".bias"], z, d, R, kin, d)
+                L.call("magpo_ln_act_fwd", z, d, v[n + ".ln.bias"], y, d, xh, d, rs, R, d, spec.act(i), st)
+                recs.append((X, ldx, kin, y, (xh, rs)))
+            else:
+                self.lin(X, ldx, Wt, v[n + ".bias"], y, d, R, kin, d, act=spec.act(i))
+                recs.append((X, ldx, kin, y, None))
+            X, ldx, kin = y, d, d
+        return recs
+
+    def _torso_bwd(self, prefix, spec, recs, dy):
+        """Backward through one torso.  ``dy`` = gradient at the last layer's output, already multiplied by that layer's activation
+        derivative when the layer has no LayerNorm (the GEMM that produced it fused the mask: act 4 / 6).  Fills the layers' parameter
+        gradients; returns the gradient at layer 0's pre-activation (the small first layer: at its output, unmasked)."""
+        L, st, gv, v, b = self.L, self._st(), self.gv, self.v, self.b
+        R = dy.shape[0]
+        for i in range(len(spec.layer_sizes) - 1, -1, -1):
+            n = layer_name(prefix, i)
+            d = spec.layer_sizes[i]
+            X, ldx, kin, y, ln = recs[i]
+            if prefix == "pre" and i == 0 and self.small_first:
+                return dy
+            if ln is not None:   # LayerNorm + activation backward on the rows; the LayerNorm bias gradient from per-workgroup slabs
+                dz = b.get(f"g_{prefix}{i}.dz", (R, d))
+                grid = L.call("magpo_row_grid", R)
+                slab = b.get(f"g_{prefix}{i}.slab", (grid, d))
+                L.call("magpo_ln_act_bwd", dy, d, y, d, ln[0], d, ln[1], dz, d, slab, R, d, spec.act(i), st)
+                self.reduce(slab, gv[n + ".ln.bias"])
+            else:
+                dz = dy
+            krows = self.F if (prefix == "pre" and i == 0) else None
+            self.wgrad(X, ldx, dz, d, R, kin, d, gv[n + ".kernel"], gv[n + ".bias"], krows=krows)
+            if i == 0:
+                return dz
+            dy = b.get(f"g_{prefix}{i - 1}.dy", (R, spec.layer_sizes[i - 1]))
+            self._dx(dz, d, v[n + ".kernel"], d, spec.layer_sizes[i - 1], R, dy, spec, i - 1, recs[i - 1])
+        return dy
+
+    def _dx(self, dsrc, ldsrc, W_nat, KIN, NOUT, R, dst, spec, j, rec):
+        """dst = dsrc W^T (W in its natural [NOUT, KIN] layout), times the activation derivative of layer j of ``spec`` when that
+        layer has no LayerNorm (fused epilogue: act 4 ReLU mask / act 6 tanh, its output as the mask argument)."""
+        act, M = 0, None
+        if rec[4] is None and spec.act(j):
+            act, M = (4 if spec.act(j) == 1 else 6), rec[3]
+        self.lin(dsrc, ldsrc, W_nat, None, dst, NOUT, R, KIN, NOUT, act=act, mask=M)
+
+    def _small_first_wgrad(self, obs, emb0, d0, R):
+        """Dense(F->128)+ReLU weight gradient on the raw observation rows: ``emb0`` the layer's output, ``d0`` the gradient there (unmasked)."""
+        L, b, gv, F, Hh = self.L, self.b, self.gv, self.F, 128
+        grid = L.call("magpo_row_grid", R)
+        sw = b.get("g_slabw", (grid, 33 * Hh))
+        L.call("magpo_small_relu_wgrad", obs, self.Fld, F, emb0, d0, sw, R, self._st())
+        self.reduce(sw, gv["pre.kernel"], P=F * Hh, stride=33 * Hh)
+        self.reduce(sw[:, 32 * Hh:], gv["pre.bias"], P=Hh, stride=33 * Hh)

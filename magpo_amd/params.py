@@ -425,3 +425,57 @@ def init_actor_from_key(named: Dict[str, torch.Tensor], actor_net_key: np.ndarra
         for g in ("hr", "hz", "hn"):
             put(f"gru.{g}.kernel", _orth(key(cell + (g,), 1), (H, H), 1.0))
         put("head.kernel", _orth(key(("action_head", "Dense_0"), 1), (named["head.kernel"].shape[0], K), 0.01))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Feed-forward networks (ff_ippo / ff_mappo: FeedForwardActor / FeedForwardValueNet, mava/networks/base.py:38-88): one torso and a head.
+
+def ff_layout(F: int, K: int, torso=None) -> "OrderedDict[str, Tuple[int, ...]]":
+    """Parameters of a feed-forward network: the torso's Dense layers under actor_layout's names (``pre`` / ``pre1`` / ``pre2`` ``.kernel``
+    [in, out], ``.bias``, ``<layer>.ln.bias``), then ``head.kernel`` [D, K] / ``head.bias`` (K = 1: the value head)."""
+    from .torso import DEFAULT_TORSO, layer_name
+    spec = torso or DEFAULT_TORSO
+    s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    din = F
+    for i, d in enumerate(spec.layer_sizes):
+        n = layer_name("pre", i)
+        s[n + ".kernel"] = (din, d)
+        s[n + ".bias"] = (d,)
+        if spec.use_layer_norm:
+            s[n + ".ln.bias"] = (d,)
+        din = d
+    s["head.kernel"] = (din, K)
+    s["head.bias"] = (K,)
+    return s
+
+
+def init_ff(named: Dict[str, torch.Tensor], seed: int, head_gain: float) -> None:
+    """torsos.py:42 orthogonal(sqrt2), zero biases; the head orthogonal(``head_gain``) (heads.py:53: 0.01; base.py:86: 1.0) -- from a torch
+    generator, for tests and benchmarks."""
+    gen = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for name, v in named.items():
+            if name.endswith("bias"):
+                v.zero_()
+            else:
+                v.copy_(_orthogonal(gen, tuple(v.shape), head_gain if name == "head.kernel" else math.sqrt(2.0)))
+
+
+def init_ff_from_key(named: Dict[str, torch.Tensor], net_key: np.ndarray, head_path: Tuple[str, ...], head_gain: float) -> None:
+    """The FeedForwardActor / FeedForwardValueNet parameters flax creates from ``net_key`` (ff_mappo.py:311-312), in the manner of
+    init_actor_from_key: torso layers at ("torso", "Dense_<i>") orthogonal(sqrt 2), the head at ``head_path`` -- ("action_head", "Dense_0")
+    with gain 0.01 for the actor, ("Dense_0",) with gain 1.0 for the value net -- and zero biases.  UNPINNED like the other initialisers
+    (the samplers and flax's key derivation are restated from memory, oracle/prng.py)."""
+    from .torso import layer_name
+    key = lambda path, c: _param_key(net_key, path, c)
+    with torch.no_grad():
+        def put(name, arr):
+            named[name].copy_(torch.from_numpy(np.ascontiguousarray(arr)).reshape(named[name].shape))
+        for v in named.values():
+            v.zero_()
+        i = 0
+        while layer_name("pre", i) + ".kernel" in named:
+            n = layer_name("pre", i) + ".kernel"
+            put(n, _orth(key(("torso", f"Dense_{i}"), 1), tuple(named[n].shape), math.sqrt(2.0)))
+            i += 1
+        put("head.kernel", _orth(key(tuple(head_path), 1), tuple(named["head.kernel"].shape), head_gain))

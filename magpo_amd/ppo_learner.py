@@ -60,41 +60,32 @@ class PpoGroup(Group):
         self.policy_h0 = self.critic_h0 = None                 # views of the learner's stacked start states
 
 
-class PpoLearner(AnakinLearner):
-    """The groups' rollouts are never replayed side by side as MagpoLearner.rollout does: the acting step's workspaces inside the two
-    networks and ``_gs_step`` are shared by all groups, so AnakinLearner.rollout's order, one group after the other on one stream, is
-    what keeps them apart."""
+class PpoBase(AnakinLearner):
+    """What the recurrent and the feed-forward PPO learner (ff_ppo_learner.FfPpoLearner) share: an actor and a critic with one optimiser each,
+    the critic's input rows, the key chain of a rollout, the epoch loop, the two optimiser steps and the logged loss row.  The subclass
+    supplies its networks, ``_shuffle_n`` (how many items an epoch permutes) and ``minibatch_grads(idx, group)``."""
     n_loss = 4
+    SYSTEMS = "rec_ippo / rec_mappo"
 
-    def __init__(self, env_cfg, num_envs: int, sys: SystemConfig, device, *, centralised: bool, critic_lr: Optional[float] = None,
-                 net_seed: Optional[int] = 0, wgrad_groups: int = 512, num_groups: int = 1, tuning=None, actor: Optional[GruActor] = None,
-                 critic: Optional[GruCritic] = None, optims=None, apply_fns=None, update_fns=None, actor_torso=(None, None),
-                 critic_torso=(None, None)):
-        """``centralised``: rec_mappo (the critic reads global-state rows) or rec_ippo (agents_view rows).  ``actor`` / ``critic`` /
-        ``optims`` = (actor ClipAdam, critic ClipAdam): objects built by the caller (learner_setup); by default the learner builds its
-        own from ``net_seed`` and the torso specs.  ``apply_fns`` = (actor_apply_fn, critic_apply_fn), ``update_fns`` =
-        (actor_update_fn, critic_update_fn) (rec_mappo.py:67-68): the callables the minibatch CALLS for the two training forwards and the
-        two optimiser steps -- by default the bound methods of the objects above."""
+    def __init__(self, env_cfg, num_envs: int, sys: SystemConfig, device, *, centralised: bool, tuning):
         super().__init__(env_cfg, num_envs, sys, device)
-        self.tuning = tuning if tuning is not None else (actor.tuning if actor is not None else Tuning.from_env())
-        A, K, F = self.A, self.K, self.F
+        self.tuning = tuning
         self.centralised = bool(centralised)
         if int(getattr(sys, "micro_batches", 1) or 1) != 1:
-            raise NotImplementedError("system.micro_batches is not supported by rec_ippo / rec_mappo")
+            raise NotImplementedError(f"system.micro_batches is not supported by {self.SYSTEMS}")
         # what the critic reads: agents_view rows, or global-state rows of num_agents * raw features (zero-padded to gs_ld)
         self.F_raw = raw_features(env_cfg)
         if self.centralised:
-            self.gs_ld = global_state_ld(A, self.F_raw)    # raises beyond 128 inputs
-            cF, cld = A * self.F_raw, self.gs_ld
+            self.gs_ld = global_state_ld(self.A, self.F_raw)    # raises beyond 128 inputs
+            self.cF, self.cld = self.A * self.F_raw, self.gs_ld
         else:
             self.gs_ld = 0
-            cF, cld = F, self.Fld
-        if actor is None:
-            actor = GruActor(A, K, F, device, wgrad_groups=wgrad_groups, seed=net_seed, tuning=self.tuning, obs_ld=self.Fld,
-                             pre_torso=actor_torso[0], post_torso=actor_torso[1])
-        if critic is None:
-            critic = GruCritic(A, cF, device, centralised=self.centralised, wgrad_groups=wgrad_groups, seed=None if net_seed is None else net_seed + 1,
-                               tuning=self.tuning, obs_ld=cld, pre_torso=critic_torso[0], post_torso=critic_torso[1])
+            self.cF, self.cld = self.F, self.Fld
+
+    def _bind_networks(self, actor, critic, sys: SystemConfig, critic_lr, optims, apply_fns, update_fns, num_groups: int):
+        """Check the networks against the system, lay their gradients into one all-reduce message, build / take the optimisers and the four
+        callables of get_learner_fn."""
+        F, cF, cld, device = self.F, self.cF, self.cld, self.dev
         if actor.F != F or actor.Fld != self.Fld or critic.F != cF or critic.Fld != cld or critic.centralised != self.centralised:
             raise ValueError(f"networks built for {actor.F} / {critic.F} input features with row strides {actor.Fld} / {critic.Fld}; this system "
                              f"needs {F} / {cF} with row strides {self.Fld} / {cld} (centralised critic: {self.centralised})")
@@ -113,15 +104,8 @@ class PpoLearner(AnakinLearner):
         assert self.a_opt.net is actor and self.c_opt.net is critic
         self.actor_apply_fn, self.critic_apply_fn = apply_fns if apply_fns is not None else (actor.apply, critic.apply)
         self.actor_update_fn, self.critic_update_fn = update_fns if update_fns is not None else (self.a_opt.update, self.c_opt.update)
-        self.groups: List[PpoGroup] = [PpoGroup(env_cfg, num_envs, self.T, device) for _ in range(num_groups)]
-        U_, N_ = num_groups, num_envs
-        self._policy_h0 = torch.zeros(U_ * N_ * A, 128, device=device)   # rollout-start states of all groups, stacked (h0 + h0_idx of the scans)
-        self._critic_h0 = torch.zeros(U_ * N_ * A, 128, device=device)
-        for gi, g in enumerate(self.groups):
-            g.policy_h0 = self._policy_h0[gi * N_ * A:(gi + 1) * N_ * A]
-            g.critic_h0 = self._critic_h0[gi * N_ * A:(gi + 1) * N_ * A]
-        self._ident_perm = torch.arange(A, dtype=torch.int32, device=device)   # PPO does not permute agents
-        self._gs_step = torch.zeros(num_envs, A, self.gs_ld, device=device) if self.centralised else None
+        self._ident_perm = torch.arange(self.A, dtype=torch.int32, device=device)   # PPO does not permute agents
+        self._gs_step = torch.zeros(self.N, self.A, self.gs_ld, device=device) if self.centralised else None
 
     def _critic_rows(self, obs_rows: torch.Tensor, n_env: int, out: Optional[torch.Tensor]) -> torch.Tensor:
         """The critic's input rows for ``n_env`` x A stored observation rows: the rows themselves, or their global state in ``out``."""
@@ -130,20 +114,93 @@ class PpoLearner(AnakinLearner):
         self.L.call("magpo_global_state", obs_rows, self.Fld, self.A, self.F_raw, out, self.gs_ld, n_env, self.A, self._st())
         return out
 
-    def _reset_states(self, g: PpoGroup):
-        """Both hidden states start at zero (ScannedRNN.initialize_carry, rec_mappo.py:455-460)."""
-        g.policy_h[0].zero_()
-        g.critic_h[0].zero_()
-
-    # ------------------------------------------------------------------ rollout (rec_mappo.py:92-166)
-    def _rollout_keys(self, g: PpoGroup):
-        """Host key chain of one rollout: key, policy_key = split(key) per env step (rec_mappo.py:106)."""
+    def _rollout_keys(self, g: Group):
+        """Host key chain of one rollout: key, policy_key = split(key) per env step (rec_mappo.py:106 = ff_mappo.py:83)."""
         key = g.key
         for t in range(self.T):
             ks = host_split(key, 2)
             key, g.keys_host[t] = ks[0], ks[1]
         g.key = key
 
+    def apply_grads(self, grad_scale: float = 1.0):
+        """Two optax chains clip_by_global_norm + adam (rec_mappo.py:435-442, :268-277)."""
+        self.c_opt.sys.lr_num_updates = self.sys.lr_num_updates
+        self.last_lr = self.actor_update_fn(grad_scale, self.ws64, self.gnorm[0:1])
+        self.critic_update_fn(grad_scale, self.ws64, self.gnorm[1:2])
+
+    def _shuffle_n(self) -> int:
+        """Items one epoch permutes and cuts into num_minibatches slices."""
+        raise NotImplementedError
+
+    # ------------------------------------------------------------------ update (rec_mappo.py:168-350)
+    def update(self, grad_sync: Optional[Callable[["PpoBase"], float]] = None) -> torch.Tensor:
+        """ppo_epochs x num_minibatches optimisation steps; returns the loss table [P, M, 4] (device) in the order of LOSS_NAMES with the
+        reference's logging quirk (rec_mappo.py:282-291): ``actor_loss`` is the actor's TOTAL (surrogate - ent_coef * entropy),
+        ``value_loss`` the unscaled one, ``total_loss`` = actor total + vf_coef * value_loss."""
+        s, n = self.sys, self._shuffle_n()
+        M = s.num_minibatches
+        mbs = n // M
+        losses = torch.zeros(s.ppo_epochs, M, self.n_loss, device=self.dev)
+        for e in range(s.ppo_epochs):
+            ks = host_split(self.groups[0].key, 3)    # every group holds the same key => one permutation serves all groups
+            kb, ke = ks[1], ks[2]
+            for g in self.groups:
+                g.key = ks[0].copy()
+            batch_perm = self._permutation(kb, n)
+            for mi in range(M):
+                ke = host_split(ke, 2)[1]  # key, entropy_key = split(key); entropy_key is what the scan carries (:235,293), unused for discrete actions
+                idx = batch_perm[mi * mbs:(mi + 1) * mbs].contiguous()
+                self._optimise(lambda group: self.minibatch_grads(idx, group), grad_sync, losses[e, mi])
+        return losses
+
+    def _loss_row(self, row: torch.Tensor):
+        """loss_out [total, surrogate, entropy, value_loss] in the order and with the quirk ``update`` documents."""
+        lo = self.loss_out
+        row[0].copy_(lo[0]); row[1].copy_(lo[3]); row[3].copy_(lo[2])
+        torch.sub(lo[1], lo[2], alpha=self.sys.ent_coef, out=row[2])
+
+
+class PpoLearner(PpoBase):
+    """The groups' rollouts are never replayed side by side as MagpoLearner.rollout does: the acting step's workspaces inside the two
+    networks and ``_gs_step`` are shared by all groups, so AnakinLearner.rollout's order, one group after the other on one stream, is
+    what keeps them apart."""
+
+    def __init__(self, env_cfg, num_envs: int, sys: SystemConfig, device, *, centralised: bool, critic_lr: Optional[float] = None,
+                 net_seed: Optional[int] = 0, wgrad_groups: int = 512, num_groups: int = 1, tuning=None, actor: Optional[GruActor] = None,
+                 critic: Optional[GruCritic] = None, optims=None, apply_fns=None, update_fns=None, actor_torso=(None, None),
+                 critic_torso=(None, None)):
+        """``centralised``: rec_mappo (the critic reads global-state rows) or rec_ippo (agents_view rows).  ``actor`` / ``critic`` /
+        ``optims`` = (actor ClipAdam, critic ClipAdam): objects built by the caller (learner_setup); by default the learner builds its
+        own from ``net_seed`` and the torso specs.  ``apply_fns`` = (actor_apply_fn, critic_apply_fn), ``update_fns`` =
+        (actor_update_fn, critic_update_fn) (rec_mappo.py:67-68): the callables the minibatch CALLS for the two training forwards and the
+        two optimiser steps -- by default the bound methods of the objects above."""
+        super().__init__(env_cfg, num_envs, sys, device, centralised=centralised,
+                         tuning=tuning if tuning is not None else (actor.tuning if actor is not None else Tuning.from_env()))
+        A, K, F = self.A, self.K, self.F
+        if actor is None:
+            actor = GruActor(A, K, F, device, wgrad_groups=wgrad_groups, seed=net_seed, tuning=self.tuning, obs_ld=self.Fld,
+                             pre_torso=actor_torso[0], post_torso=actor_torso[1])
+        if critic is None:
+            critic = GruCritic(A, self.cF, device, centralised=self.centralised, wgrad_groups=wgrad_groups, seed=None if net_seed is None else net_seed + 1,
+                               tuning=self.tuning, obs_ld=self.cld, pre_torso=critic_torso[0], post_torso=critic_torso[1])
+        self._bind_networks(actor, critic, sys, critic_lr, optims, apply_fns, update_fns, num_groups)
+        self.groups: List[PpoGroup] = [PpoGroup(env_cfg, num_envs, self.T, device) for _ in range(num_groups)]
+        U_, N_ = num_groups, num_envs
+        self._policy_h0 = torch.zeros(U_ * N_ * A, 128, device=device)   # rollout-start states of all groups, stacked (h0 + h0_idx of the scans)
+        self._critic_h0 = torch.zeros(U_ * N_ * A, 128, device=device)
+        for gi, g in enumerate(self.groups):
+            g.policy_h0 = self._policy_h0[gi * N_ * A:(gi + 1) * N_ * A]
+            g.critic_h0 = self._critic_h0[gi * N_ * A:(gi + 1) * N_ * A]
+
+    def _shuffle_n(self) -> int:
+        return self.N   # the N sequences (rec_mappo.py:311-321)
+
+    def _reset_states(self, g: PpoGroup):
+        """Both hidden states start at zero (ScannedRNN.initialize_carry, rec_mappo.py:455-460)."""
+        g.policy_h[0].zero_()
+        g.critic_h[0].zero_()
+
+    # ------------------------------------------------------------------ rollout (rec_mappo.py:92-166)
     def _rollout_body(self, g: PpoGroup, pkeys):
         """T acting steps, the bootstrap value and GAE, all on the current stream (no parallel branches in the captured graph).  The
         carried hidden states are in policy_h[0] / critic_h[0] before and after (T is even or odd: the last state is copied back)."""
@@ -196,36 +253,3 @@ class PpoLearner(AnakinLearner):
                     m["da"], 64, m["dv"], self.ws64, self.loss_out, R, K, s.clip_eps, s.ent_coef, s.vf_coef, self._st())
         self.actor.seq_bwd(m["da"])
         self.critic.seq_bwd(m["dv"])    # dvalue is d(vf_coef * value_loss): the critic's total loss (rec_mappo.py:231)
-
-    def apply_grads(self, grad_scale: float = 1.0):
-        """Two optax chains clip_by_global_norm + adam (rec_mappo.py:435-442, :268-277)."""
-        self.c_opt.sys.lr_num_updates = self.sys.lr_num_updates
-        self.last_lr = self.actor_update_fn(grad_scale, self.ws64, self.gnorm[0:1])
-        self.critic_update_fn(grad_scale, self.ws64, self.gnorm[1:2])
-
-    # ------------------------------------------------------------------ update (rec_mappo.py:168-350)
-    def update(self, grad_sync: Optional[Callable[["PpoLearner"], float]] = None) -> torch.Tensor:
-        """ppo_epochs x num_minibatches optimisation steps; returns the loss table [P, M, 4] (device) in the order of LOSS_NAMES with the
-        reference's logging quirk (rec_mappo.py:282-291): ``actor_loss`` is the actor's TOTAL (surrogate - ent_coef * entropy),
-        ``value_loss`` the unscaled one, ``total_loss`` = actor total + vf_coef * value_loss."""
-        s, N = self.sys, self.N
-        M = s.num_minibatches
-        mbs = N // M
-        losses = torch.zeros(s.ppo_epochs, M, self.n_loss, device=self.dev)
-        for e in range(s.ppo_epochs):
-            ks = host_split(self.groups[0].key, 3)    # every group holds the same key => one permutation serves all groups
-            kb, ke = ks[1], ks[2]
-            for g in self.groups:
-                g.key = ks[0].copy()
-            batch_perm = self._permutation(kb, N)
-            for mi in range(M):
-                ke = host_split(ke, 2)[1]  # key, entropy_key = split(key); entropy_key is what the scan carries (:235,293), unused for discrete actions
-                idx = batch_perm[mi * mbs:(mi + 1) * mbs].contiguous()
-                self._optimise(lambda group: self.minibatch_grads(idx, group), grad_sync, losses[e, mi])
-        return losses
-
-    def _loss_row(self, row: torch.Tensor):
-        """loss_out [total, surrogate, entropy, value_loss] in the order and with the quirk ``update`` documents."""
-        lo = self.loss_out
-        row[0].copy_(lo[0]); row[1].copy_(lo[3]); row[3].copy_(lo[2])
-        torch.sub(lo[1], lo[2], alpha=self.sys.ent_coef, out=row[2])

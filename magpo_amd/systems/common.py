@@ -18,7 +18,7 @@ from magpo_amd import distributed as mdist
 from magpo_amd.actor import GruActor
 from magpo_amd.anakin import SystemConfig
 from magpo_amd.envs import host_split, obs_row_stride
-from magpo_amd.evaluator import get_eval_fn, get_num_eval_envs, make_rec_eval_act_fn
+from magpo_amd.evaluator import get_eval_fn, get_num_eval_envs, make_ff_eval_act_fn, make_rec_eval_act_fn
 from magpo_amd.torso import DEFAULT_TORSO, torso_from_config
 from magpo_amd.types import ExperimentOutput
 from magpo_amd.utils.checkpointing import Checkpointer, latest_valid_checkpoint, load_checkpoint, restore_learner_state
@@ -165,6 +165,16 @@ def train_and_evaluate_gru_actor(config, env, eval_env, learn, actor_network, le
     return train_and_evaluate(config, env, eval_env, learn, learner_state, make_rec_eval_act_fn(eval_actor, config), key, key_e, device, rank, world,
                               init_act_state=lambda batch: {"hidden_state": torch.zeros(batch * env.num_agents, 128, device=device)},
                               eval_params=lambda state: state.params.actor_params)
+
+
+def train_and_evaluate_ff_actor(config, env, eval_env, learn, actor_network, learner_state, key, key_e, device, rank, world) -> float:
+    """``train_and_evaluate`` for a system whose evaluated policy is an FfActor (ff_ippo, ff_mappo): a second actor object of the same torso
+    on the evaluator's own batch of envs, with the pre-interval ``params.actor_params``; the actor state is ``{}``."""
+    from magpo_amd.ff_nets import FfActor
+    eval_actor = FfActor(env.num_agents, env.action_dim, env.obs_dim, device, obs_ld=obs_row_stride(env.cfg.obs_dim), torso=actor_network.spec,
+                         tuning=actor_network.tuning)
+    return train_and_evaluate(config, env, eval_env, learn, learner_state, make_ff_eval_act_fn(eval_actor, config), key, key_e, device, rank, world,
+                              init_act_state=lambda batch: {}, eval_params=lambda state: state.params.actor_params)
 
 
 def train_and_evaluate(config, env, eval_env, learn, learner_state, eval_act_fn, key, key_e, device, rank, world, *, init_act_state, eval_params) -> float:

@@ -1,4 +1,4 @@
-"""Pytree surface of the recurrent PPO systems on torch tensors (mava/systems/ppo/types.py).
+"""Pytree surface of the PPO systems (recurrent and feed-forward) on torch tensors (mava/systems/ppo/types.py).
 
 Same names and fields as the reference NamedTuples.  Leaves are device tensors with a leading group axis (the reference's update-batch
 axis); parameters are the networks' named views (magpo_amd/params.py: actor_named_views), optimiser states the flat optax-adam triple."""
@@ -22,6 +22,25 @@ class OptStates(NamedTuple):
 class HiddenStates(NamedTuple):
     policy_hidden_state: torch.Tensor    # [groups, N * A, 128]
     critic_hidden_state: torch.Tensor
+
+
+class LearnerState(NamedTuple):
+    """State of the feed-forward systems (ff_ippo / ff_mappo)."""
+    params: Params
+    opt_states: OptStates
+    key: Any
+    env_state: Any
+    timestep: Any                        # agents_view, step_count[, action_mask]
+    dones: torch.Tensor                  # [groups, N] u8: timestep.last(), repeated over the agents inside the kernels
+
+
+class PPOTransition(NamedTuple):
+    done: torch.Tensor
+    action: torch.Tensor
+    value: torch.Tensor
+    reward: torch.Tensor
+    log_prob: torch.Tensor
+    obs: Any
 
 
 class RNNLearnerState(NamedTuple):

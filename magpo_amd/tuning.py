@@ -21,6 +21,9 @@ Environment variables are read HERE, once, when the default instance is built (A
     MAGPO_PPO_FUSED_STEP=0|1    acting step of rec_ippo / rec_mappo: 1 = both GRU cells in one magpo_gru_cell_step launch (csrc/gru_step.hip), 0 = the
                                 composed GruActor.step of each network (magpo_linear for xi + a T = 1 scan).  Same function, fp32 summation order differs.
                                 Default: see Tuning.ppo_fused_step
+    MAGPO_FF_FUSED_STEP=0|1     acting step of ff_ippo / ff_mappo: 1 = torso and head of both networks in one magpo_mlp_act_step launch (csrc/mlp_step.hip),
+                                0 = the composed chain of dense kernels per network.  Same function, same fp32 summation order.
+                                Default: see Tuning.ff_fused_step
 """
 from __future__ import annotations
 
@@ -38,6 +41,7 @@ class Tuning:
     wgrad_variant: int = 0        # magpo_wgrad (0, or 64 = bf16 triples for 128 x 384)
     act_envs_per_wave: int = 0    # magpo_sable_act dims[11]
     ppo_fused_step: bool = True   # critic.step_pair: magpo_gru_cell_step (True) or the composed step of each network (False)
+    ff_fused_step: bool = True    # ff_nets.act_pair: magpo_mlp_act_step (True) or the composed dense chain of each network (False)
 
     @classmethod
     def from_env(cls, env=None) -> "Tuning":
@@ -51,4 +55,5 @@ class Tuning:
         t.wgrad_variant = 64 if on("MAGPO_WGRAD_BF3") else 0
         t.act_envs_per_wave = int(e["MAGPO_ACT_EPW"]) if e.get("MAGPO_ACT_EPW") in ("4", "8", "16") else 0
         t.ppo_fused_step = e["MAGPO_PPO_FUSED_STEP"] == "1" if e.get("MAGPO_PPO_FUSED_STEP") in ("0", "1") else cls().ppo_fused_step
+        t.ff_fused_step = e["MAGPO_FF_FUSED_STEP"] == "1" if e.get("MAGPO_FF_FUSED_STEP") in ("0", "1") else cls().ff_fused_step
         return t

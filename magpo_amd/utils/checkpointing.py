@@ -217,6 +217,11 @@ def restore_learner_state(path: str, device="cuda", rank: int = 0, world: int = 
             return {k: dev(v) for k, v in x.items()}
         return x
 
+    if "hstates" not in st:   # the feed-forward PPO systems (systems/ppo/types.py: LearnerState): nothing is carried between env steps
+        from ..systems.ppo import types as ppo
+        return ppo.LearnerState(ppo.Params(dev(st["params"]["actor_params"]), dev(st["params"]["critic_params"])),
+                                ppo.OptStates(dev(st["opt_states"]["actor_opt_state"]), dev(st["opt_states"]["critic_opt_state"])),
+                                st["key"], dev(st["env_state"]), dev(st["timestep"]), dev(st["dones"])), int(ck["timestep"])
     hs = st["hstates"]
     if "dones" not in st:   # the guider-only system (systems/sable/types.py: RecLearnerState)
         from ..systems.sable.types import HiddenStates as SableHS, LearnerState as SableLearnerState
