@@ -229,6 +229,20 @@ int magpo_retention_recurrent(float* S, const float* q, long ldq, const float* k
                               int hs, int gs, magpo_stream_t stream);
 int magpo_zero_states_where_done(float* s0, float* s1, float* s2, const unsigned char* done, int nenv,
                                  magpo_stream_t stream);
+/* stateless retention over nteams independent teams of A consecutive token rows (retention.py:79-84, 94-99 with memory_config.type
+ * "ff_sable" on a zero hidden state; csrc/team_retention.hip): r_i = sum_j M_ij (q_i . k_j) v_j over the rows i, j of one team, M_ij = [j <= i]
+ * when masked, else 1.  No decay, no carried state: nothing is read but the operands and nothing is written but r (dq | dk | dv).
+ * 1 <= A <= 32; hs = tile width in 1..64 (a head, or one 64-wide block of a wider head: the masked product is linear in the q / k blocks);
+ * row strides multiples of 4 floats.  ntok / ret_from as in magpo_retention_recurrent: only rows ret_from <= i < ntok of every team are
+ * produced, from the k / v rows j < ntok (training: ntok = A, ret_from = 0; decoder iteration i of acting: ntok = i + 1, ret_from = i).
+ * gp (nullable) selects magpo_retention_recurrent's fused GroupNorm + swish-gate epilogue, with the same gamma / beta / gs contract.
+ * bwd: dP = (dr v^T) * M, dq = dP k, dk = dP^T q, dv = ((q k^T) * M)^T dr, every row of every team. */
+int magpo_team_retention_fwd(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, float* r, long ldr,
+                             long nteams, int A, int ntok, int ret_from, int masked, int hs, const float* gp, long ldg,
+                             const float* gamma, const float* beta, int gs, magpo_stream_t stream);
+int magpo_team_retention_bwd(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, const float* dr, long lddr,
+                             float* dq, long lddq, float* dk, long lddk, float* dv, long lddv, long nteams, int A, int masked,
+                             int hs, magpo_stream_t stream);
 
 /* ---- K2 fused acting step: SableNetwork.get_actions (sable_network.py:443-482; decode.py:111-153) in ONE launch ----
  * dims_host[16] = {N, A, K, F, n_block, n_head, hs, gs, npos, value_only, obs row stride (>= F), envs per wave (0 = by size, or 4 / 8 / 16),

@@ -42,7 +42,15 @@ class SableGuider(NetBase):
     def __init__(self, n_agents: int, action_dim: int, obs_dim: int, device, *, embed_dim: int = 64, n_head: int = 1,
                  n_block: int = 1, decay_scaling_factor: float = 0.8, use_pe: bool = True, max_pos: int = 101,
                  wgrad_groups: int = 512, seed: Optional[int] = None, grads: Optional[torch.Tensor] = None,
-                 tuning: Optional[Tuning] = None, obs_ld: Optional[int] = None):
+                 tuning: Optional[Tuning] = None, obs_ld: Optional[int] = None, memory_type: str = "rec_sable"):
+        if memory_type not in ("rec_sable", "ff_sable"):
+            raise NotImplementedError(f"memory_type must be rec_sable or ff_sable, got {memory_type!r}")
+        # ff_sable (mava/systems/sable/anakin/ff_sable.py): retention over the agents of ONE time step on zero hidden states -- no decay
+        # (:341), no timestep positional encoding (:350; an all-zero pe table makes the existing kernels add exactly 0), no state buffers:
+        # every retention op is a team kernel (csrc/team_retention.hip)
+        self.memory_type, self.ff = memory_type, memory_type == "ff_sable"
+        if self.ff:
+            decay_scaling_factor, use_pe = 1.0, False
         if embed_dim not in (16, 32, 64, 128) or n_head not in (1, 2, 4) or n_block < 1 or embed_dim % n_head or 64 // n_head // n_head < 4:
             raise NotImplementedError("gfx950 Sable kernels: embed_dim in {16, 32, 64, 128} (nets narrower than 64 run embedded in the 64-wide "
                                       "kernels, params.WidthEmbedding) and n_head in {1, 2, 4} (SURVEY 8f rank 3)")
@@ -58,7 +66,7 @@ class SableGuider(NetBase):
             raise NotImplementedError("obs_dim <= 128 and action_dim <= 31 required")
         super().__init__(obs_dim, device, wgrad_groups, tuning, obs_ld)
         self.A, self.K = n_agents, action_dim
-        self.kappas = decay_kappas(self.nh, decay_scaling_factor)
+        self.kappas = [1.0] * self.nh if self.ff else decay_kappas(self.nh, decay_scaling_factor)
         self.kappa = self.kappas[0]
         # P / grads: the LOGICAL parameters (optimiser, all-reduce, checkpoints); PD / grads_D: what the kernels read and write.
         # For embed_dim = 64 they are the same buffers.
@@ -233,8 +241,12 @@ class SableGuider(NetBase):
         self.L.call("magpo_add_rows", dst, ldd, src, lds, R, W, self._st())
 
     def _ret_rec(self, S, q, ldq, k, ldk, v, ldv, env_rows, u, ldu, N, ntok, ret_from, write, gp, ldg, gamma, beta):
-        """Recurrent retention + GroupNorm / gate for every state tile; S [ntile, N, 64, 64].  Rows: token a of env e at e * env_rows + a."""
+        """Recurrent retention + GroupNorm / gate for every state tile; S [ntile, N, 64, 64].  Rows: token a of env e at e * env_rows + a.
+        ff_sable: the same rows from the stateless team kernel (S, write unused; the rows of an env are consecutive)."""
         E = self.E
+        if self.ff:
+            assert env_rows == self.A
+            return self._team_ret_act(q, ldq, k, ldk, v, ldv, u, ldu, N, ntok, ret_from, gp, ldg, gamma, beta)
         if not self.blockwise:   # the kernel's fused epilogue covers a whole head
             for ti, oq, ov, w, kap in self._tiles():
                 self.L.call("magpo_retention_recurrent", S[ti], q[:, oq:], ldq, k[:, oq:], ldk, v[:, ov:], ldv, env_rows, u[:, ov:], ldu, N, ntok,
@@ -253,8 +265,65 @@ class SableGuider(NetBase):
             self.L.call("magpo_retpost_fwd", raw[a:], env_rows * E, gp[a:], env_rows * ldg, gamma, beta, u[a:], env_rows * ldu, N, self.hs, self.gs,
                         E, self._st())
 
+    # ---- ff_sable: stateless retention over teams of A consecutive rows (csrc/team_retention.hip); same tiles, no state anywhere
+    def _team_ret_act(self, q, ldq, k, ldk, v, ldv, u, ldu, N, ntok, ret_from, gp, ldg, gamma, beta):
+        """Acting: rows ret_from <= a < ntok of every env from its k / v rows a < ntok, then GroupNorm + swish gate (fused into the kernel
+        when a tile is a whole head).  The decoder asks for its newest token only, so the causal mask is implied by ntok."""
+        E, A, st = self.E, self.A, self._st()
+        masked = 0 if ret_from == 0 else 1
+        if not self.blockwise:
+            for _, oq, ov, w, _ in self._tiles():
+                self.L.call("magpo_team_retention_fwd", q[:, oq:], ldq, k[:, oq:], ldk, v[:, ov:], ldv, u[:, ov:], ldu, N, A, ntok, ret_from, masked, w,
+                            gp[:, ov:], ldg, gamma, beta, self.gs, st)
+            return
+        R = u.shape[0]
+        raw, tmp = self.b.get("rr_raw", (R, E)), self.b.get("rr_tmp", (R, TILE))
+        for _, oq, ov, w, _ in self._tiles():
+            first = oq == 0
+            out, ldo = (raw[:, ov:], E) if first else (tmp, TILE)
+            self.L.call("magpo_team_retention_fwd", q[:, oq:], ldq, k[:, oq:], ldk, v[:, ov:], ldv, out, ldo, N, A, ntok, ret_from, masked, w,
+                        None, 0, None, None, 0, st)
+            if not first:
+                self.add_rows(raw[:, ov:], E, tmp, TILE, R, TILE)   # (rows outside [ret_from, ntok) hold stale values: never read)
+        for a in range(ret_from, ntok):
+            self.L.call("magpo_retpost_fwd", raw[a:], A * E, gp[a:], A * ldg, gamma, beta, u[a:], A * ldu, N, self.hs, self.gs, E, st)
+
+    def _team_ret_fwd(self, q, ldq, k, ldk, v, ldv, r, nteams, masked):
+        E, R = self.E, nteams * self.A
+        for _, oq, ov, w, _ in self._tiles():
+            partial = self.blockwise and oq != 0
+            out, ldo = (self.b.get("rf_tmp", (R, TILE)), TILE) if partial else (r[:, ov:], E)
+            self.L.call("magpo_team_retention_fwd", q[:, oq:], ldq, k[:, oq:], ldk, v[:, ov:], ldv, out, ldo, nteams, self.A, self.A, 0, masked, w,
+                        None, 0, None, None, 0, self._st())
+            if partial:
+                self.add_rows(r[:, ov:], E, out, TILE, R, TILE)
+
+    def _team_ret_bwd(self, q, ldq, k, ldk, v, ldv, dr, dq, lddq, dk, lddk, dv, lddv, nteams, masked):
+        E, R = self.E, nteams * self.A
+        for _, oq, ov, w, _ in self._tiles():
+            if not self.blockwise:
+                self.L.call("magpo_team_retention_bwd", q[:, oq:], ldq, k[:, oq:], ldk, v[:, ov:], ldv, dr[:, ov:], E, dq[:, oq:], lddq, dk[:, oq:],
+                            lddk, dv[:, ov:], lddv, nteams, self.A, masked, w, self._st())
+                continue
+            # block (I, J) of the 128-wide head: dq_I, dk_I add over J; dv_J adds over I
+            tq, tk, tv = (self.b.get(f"rb_t{c}", (R, TILE)) for c in "qkv")
+            qk_first, v_first = ov == 0, oq == 0
+            oq_, ldq_ = (dq[:, oq:], lddq) if qk_first else (tq, TILE)
+            ok_, ldk_ = (dk[:, oq:], lddk) if qk_first else (tk, TILE)
+            ov_, ldv_ = (dv[:, ov:], lddv) if v_first else (tv, TILE)
+            self.L.call("magpo_team_retention_bwd", q[:, oq:], ldq, k[:, oq:], ldk, v[:, ov:], ldv, dr[:, ov:], E, oq_, ldq_, ok_, ldk_, ov_, ldv_,
+                        nteams, self.A, masked, w, self._st())
+            if not qk_first:
+                self.add_rows(dq[:, oq:], lddq, tq, TILE, R, TILE)
+                self.add_rows(dk[:, oq:], lddk, tk, TILE, R, TILE)
+            if not v_first:
+                self.add_rows(dv[:, ov:], lddv, tv, TILE, R, TILE)
+
     def _ret_fwd(self, q, ldq, k, ldk, v, ldv, r, s0, seq_env, dones, name, nseq, T, masked, rows=None):
         """``rows`` (i32 [R], optional): q | k | v are row tables and token row r reads table row rows[r] (csrc/classtab.hip)."""
+        if self.ff:   # no t_* state buffers, no s0, no dones
+            assert T == 1 and rows is None
+            return self._team_ret_fwd(q, ldq, k, ldk, v, ldv, r, nseq, masked)
         ct = self.tuning.ret_chunk_tokens
         nch = self.L.call("magpo_retention_num_chunks", T, self.A, ct)
         E, R = self.E, nseq * T * self.A
@@ -268,6 +337,9 @@ class SableGuider(NetBase):
                 self.add_rows(r[:, ov:], E, out, TILE, R, TILE)
 
     def _ret_bwd(self, q, ldq, k, ldk, v, ldv, dr, dq, lddq, dk, lddk, dv, lddv, dones, name, nseq, T, masked, rows=None):
+        if self.ff:
+            assert T == 1 and rows is None
+            return self._team_ret_bwd(q, ldq, k, ldk, v, ldv, dr, dq, lddq, dk, lddk, dv, lddv, nseq, masked)
         ct = self.tuning.ret_chunk_tokens
         E, R = self.E, nseq * T * self.A
         for ti, oq, ov, w, kap in self._tiles():
@@ -302,8 +374,11 @@ class SableGuider(NetBase):
         v, b = self.v, self.b
         xn = b.get("a_xn", (R, E)); qkvg = b.get("a_qkvg", (R, 4 * E)); u = b.get("a_u", (R, E)); y = b.get("a_y", (R, E))
         rep = b.get("a_rep", (R, E)); reppe = b.get("a_reppe", (R, E)); hv = b.get("a_hv", (R, E))
-        s_enc, s_d1, s_d2 = states
-        if value_only:  # bootstrap value (rec_magpo.py:202-208): states must not change
+        if self.ff:   # memoryless: ``states`` is not read (pass None)
+            s_enc = s_d1 = s_d2 = [None] * nb
+        else:
+            s_enc, s_d1, s_d2 = states
+        if value_only and not self.ff:  # bootstrap value (rec_magpo.py:202-208): states must not change
             s_enc = b.get("a_senc_tmp", tuple(s_enc.shape)).copy_(s_enc)
         pos_tok = b.get("a_pos", (R,), torch.int32)
         pos_tok.view(N, A).copy_(pos.view(N, 1).expand(N, A))
@@ -387,6 +462,9 @@ class SableGuider(NetBase):
         ``defer`` / ``precand`` (include/magpo.h): inside a rollout half of the workgroups run the block-0 candidate pre-pass of the NEXT
         step at the end of the launch (defer) and skip it in the next one (precand), so that they stream states while the others decode."""
         A, K, F, nb, nh = self.A, self.K, self.F, self.nb, self.nh
+        if self.ff:
+            raise NotImplementedError("ff_sable acts through SableGuider.act (one team-retention launch per retention op); a one-launch "
+                                      "stateless acting kernel is not built")
         if A > 8 or self.E != 64:   # token staging registers / 64-wide register rows of the fused kernel: larger teams take the kernel-by-kernel path (states settled on return)
             if done is not None:
                 for k in range(nb):
@@ -537,6 +615,10 @@ class SableGuider(NetBase):
         Returns (logits [R,64] raw with K valid columns, value [R])."""
         L, st, A, K, F, v, b, nb, E = self.L, self._st(), self.A, self.K, self.F, self.v, self.b, self.nb, self.E
         R = nseq * T * A
+        if self.ff:   # items of one time step: no start states, no dones, dense first layers
+            if T != 1 or classes is not None:
+                raise ValueError("ff_sable trains on single time steps (T = 1) without class tables")
+            s0 = ((None,) * nb,) * 3
         g = lambda n, w=E: b.get("t_" + n, (R, w))
         direct = classes is not None and self.fused_segments   # block-0 consumers read the class tables through the class index
         self._saved = dict(obs=obs, prev_idx=prev_idx, pos=pos, dones=dones, nseq=nseq, T=T, R=R, classes=classes, direct=direct)

@@ -31,6 +31,14 @@ class RecLearnerState(NamedTuple):
     hstates: HiddenStates
 
 
+class FFLearnerState(NamedTuple):     # ff_sable: nothing is carried between env steps but the env itself
+    params: Dict[str, torch.Tensor]
+    opt_states: Dict[str, Any]
+    key: Any
+    env_state: Any
+    timestep: Any                    # agents_view, step_count, [action_mask,] last
+
+
 class Transition(NamedTuple):        # PPOTransition
     done: torch.Tensor
     action: torch.Tensor

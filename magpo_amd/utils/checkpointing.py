@@ -217,6 +217,9 @@ def restore_learner_state(path: str, device="cuda", rank: int = 0, world: int = 
             return {k: dev(v) for k, v in x.items()}
         return x
 
+    if "hstates" not in st and "dones" not in st:   # the memoryless Sable system (systems/sable/types.py: FFLearnerState)
+        from ..systems.sable.types import FFLearnerState
+        return FFLearnerState(dev(st["params"]), dev(st["opt_states"]), st["key"], dev(st["env_state"]), dev(st["timestep"])), int(ck["timestep"])
     if "hstates" not in st:   # the feed-forward PPO systems (systems/ppo/types.py: LearnerState): nothing is carried between env steps
         from ..systems.ppo import types as ppo
         return ppo.LearnerState(ppo.Params(dev(st["params"]["actor_params"]), dev(st["params"]["critic_params"])),
