@@ -344,6 +344,36 @@ int magpo_gru_cell_step(const int* dims_host, const void* const* ptrs_host, int 
  * Rejected before any launch: R < 1, nnets not 1 or 2, nptrs != 10 nnets, layers outside 1..3, a used width outside the set, F, ldx, NOUT or
  * ldy out of range, an unknown activation code, activate_final not 0 / 1, a null pointer in a used slot. */
 int magpo_mlp_act_step(const int* dims_host, const void* const* ptrs_host, int nptrs, int R, magpo_stream_t stream);
+/* ONE acting step of the memoryless Sable (ff_sable) in a single launch (csrc/ff_sable_act.hip; SableGuider.act with memory_type "ff_sable":
+ * sable_network.py:443-482, decode.py:111-153 on zero hidden states): encoder over the A tokens of the step, value head, the A autoregressive
+ * decoder iterations with self- and cross-retention over the step's own tokens j <= i, logit head, masked log-softmax and Gumbel-argmax with the
+ * counter layout of magpo_sample_categorical (counter n K + k of agent i's key).  Stateless: kappa = 1 and a zero positional-encoding table are
+ * assumed (the caller checks both), nothing is carried between calls.  A workgroup owns 32 envs; grid ceil(N / 32).
+ *   dims_host[10] = {N, A, K, F, n_block, n_head, hs, gs, value_only, obs_ld}: 64-wide rows, hs = 64 / n_head, gs = hs / n_head; obs rows of
+ *     F features obs_ld >= F floats apart (any obs_ld; columns >= F are never read).  value_only = 1 writes value_out and nothing else.
+ *   keys_host [A][2] (agent i samples from key i), or NULL: then ptrs_host[2] is the device key table [A][2] (static arguments for graph replay).
+ *   ptrs_host[22] (device pointers):
+ *      0 obs [N][A][obs_ld]            1 mask [N][A][K] u8 (nullable)       2 keys_dev [A][2] u32 (nullable)
+ *      3 enc.obs.norm.scale [F]        4 enc.obs.dense.kernel [F][64]       5 enc.ln.scale [64]
+ *      6 dec.act.kernel [K + 1][64]    7 dec.ln.scale [64]
+ *      8 enc.head.dense0 Wt [64][64]   9 enc.head.dense0.bias [64]         10 enc.head.norm.scale [64]
+ *     11 enc.head.dense1.kernel [64]  12 enc.head.dense1.bias [1]
+ *     13 dec.head.dense0 Wt [64][64]  14 dec.head.dense0.bias [64]         15 dec.head.norm.scale [64]
+ *     16 dec.head.dense1 Wt [>= 32][64] (rows >= K zero)                   17 dec.head.dense1.bias [K]
+ *     18 scratch [scratch_floats]     19 action_out [N][A] i32             20 logp_out [N][A]         21 value_out [N][A]
+ *     (19, 20 may be null with value_only = 1)
+ *   blk_ptrs_host[18 n_block], per block (Wt = the transposed [out][64] layout magpo_transpose_pad writes):
+ *      0 enc retn.w_qkvg Wt [256][64]  1 enc retn.w_o Wt [64][64]   2 enc ln1.scale   3 enc ln2.scale   4 enc retn.gn.scale [hs]   5 enc retn.gn.bias [hs]
+ *      6 dec retn1.w_qkvg Wt [256][64] 7 dec retn1.w_o Wt [64][64]  8 dec ln1.scale   9 dec retn1.gn.scale [hs]  10 dec retn1.gn.bias [hs]
+ *     11 dec retn2.w_q Wt [64][64]    12 dec retn2.w_kvg Wt [192][64]  13 dec retn2.w_o Wt [64][64]  14 dec ln2.scale  15 dec ln3.scale
+ *     16 dec retn2.gn.scale [hs]      17 dec retn2.gn.bias [hs]
+ *   scratch: at least 32 ceil(N / 32) A (384 + 256 n_block) floats, 16-byte aligned, from the caller's workspace (never allocated inside the call);
+ *     every workgroup writes and reads only its own tile's rows.  Contents on return are unspecified.
+ * Writes exactly rows 0 .. N-1 of the outputs.  No atomics: equal inputs give identical bits.  Rejected before any launch: N < 1, A outside 1..8,
+ * n_block outside 1..4, n_head not 1 / 2 / 4 or hs / gs inconsistent with it, K outside 1..31, F outside 1..128, obs_ld < F, table sizes other than
+ * 22 / 18 n_block, a null pointer in a required slot, no keys without value_only, scratch_floats too small. */
+int magpo_ff_sable_act(const int* dims_host, const uint32_t* keys_host, const void* const* ptrs_host, int nptrs,
+                       const void* const* blk_ptrs_host, int nblk_ptrs, long scratch_floats, magpo_stream_t stream);
 /* observation.global_state of the centralised critic (mava/wrappers/matrax.py:128-131, jumanji.py:61-67): out [N A][ld], row (n, a) = the
  * concatenation over agents j of obs[(n, j)][id_cols .. id_cols + F_raw) (the raw agent views behind the id_cols leading agent-id columns of the
  * stored rows, row stride ldo), the same for every a, zero from column A F_raw to ld.  ld is 64 or 128 and A F_raw <= ld. */

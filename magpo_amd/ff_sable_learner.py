@@ -41,7 +41,8 @@ class FfSableLearner(AnakinLearner):
                  guider: Optional[SableGuider] = None, optim: Optional[ClipAdam] = None, apply_fns=None, update_fn=None):
         """``guider`` / ``optim``: the SableGuider (memory_type "ff_sable") and its ClipAdam built by the caller (ff_sable.learner_setup);
         by default the learner builds its own.  ``apply_fns`` = (sable_action_select_fn, sable_apply_fn) and ``update_fn`` as
-        get_learner_fn receives them (ff_sable.py:54-55): by default ``guider.act``, ``guider.apply`` and ``optim.update``."""
+        get_learner_fn receives them (ff_sable.py:54-55): by default ``guider.act`` (``guider.act_team_fused`` with
+        ``Tuning.ff_sable_fused_act`` on), ``guider.apply`` and ``optim.update``."""
         super().__init__(env_cfg, num_envs, sys, device)
         if int(getattr(sys, "micro_batches", 1) or 1) != 1:
             raise NotImplementedError("system.micro_batches is not supported by ff_sable")
@@ -69,7 +70,9 @@ class FfSableLearner(AnakinLearner):
         self.guider = guider
         self.g_opt = optim if optim is not None else ClipAdam(guider, sys)
         assert self.g_opt.net is guider
-        self.sable_action_select_fn, self.sable_apply_fn = apply_fns if apply_fns is not None else (guider.act, guider.apply)
+        # acting step: one magpo_ff_sable_act launch (Tuning.ff_sable_fused_act) or the kernel-by-kernel chain; the caller's functions win
+        select = guider.act_team_fused if self.tuning.ff_sable_fused_act else guider.act
+        self.sable_action_select_fn, self.sable_apply_fn = apply_fns if apply_fns is not None else (select, guider.apply)
         self.sable_update_fn = update_fn if update_fn is not None else self.g_opt.update
         self.loss_out = self.grad_all[gn:gn + self.n_loss]
         # the key table of a rollout holds the A sample keys of every env step

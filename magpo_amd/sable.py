@@ -96,6 +96,7 @@ class SableGuider(NetBase):
                 pe_l = torch.zeros(max_pos, self.EL, device=device)
                 self.L.call("magpo_pe_table", pe_l, max_pos, self.EL, self._st())
                 self.pe.copy_(self.emb.expand_rows(pe_l))
+        assert not self.ff or (not use_pe and self.kappas == [1.0] * self.nh)   # what magpo_ff_sable_act relies on: pe stays all-zero, no decay
         self.wa: Dict[str, torch.Tensor] = {}   # fragment-major copies of self.wt for the fused acting kernel: refresh() keeps both current
         self.fused_segments = self.nh == 1 and E == 64   # token-local parts between retention ops as single launches (csrc/seg_fused.hip)
         self.wg_ws = torch.empty(self.L.call("magpo_wgrad_workspace_floats", E, 4 * E, self.G), device=device)
@@ -463,8 +464,8 @@ class SableGuider(NetBase):
         step at the end of the launch (defer) and skip it in the next one (precand), so that they stream states while the others decode."""
         A, K, F, nb, nh = self.A, self.K, self.F, self.nb, self.nh
         if self.ff:
-            raise NotImplementedError("ff_sable acts through SableGuider.act (one team-retention launch per retention op); a one-launch "
-                                      "stateless acting kernel is not built")
+            raise NotImplementedError("ff_sable has no retention state to carry: its one-launch acting step is SableGuider.act_team_fused "
+                                      "(magpo_ff_sable_act), the kernel-by-kernel chain is SableGuider.act")
         if A > 8 or self.E != 64:   # token staging registers / 64-wide register rows of the fused kernel: larger teams take the kernel-by-kernel path (states settled on return)
             if done is not None:
                 for k in range(nb):
@@ -512,8 +513,51 @@ class SableGuider(NetBase):
         self.L.call("magpo_sable_act", dims.ctypes.data, kap.ctypes.data, None if keys is None else keys.ctypes.data,
                     gp.ctypes.data, int(gp.size), bp.ctypes.data, int(bp.size), self._st())
 
+    def team_fused_supported(self) -> bool:
+        """The shape set of magpo_ff_sable_act: 64-wide rows (embed_dim 16 / 32 embedded), at most 8 agents and 4 blocks."""
+        return self.ff and self.E == 64 and self.A <= 8 and self.nb <= 4
+
+    def act_team_fused(self, obs, pos, states, sample_keys, action_out, logp_out, value_out, mask=None, value_only=False):
+        """:meth:`act` of a memoryless network (memory_type "ff_sable") in ONE launch per env step (csrc/ff_sable_act.hip: a workgroup
+        carries 32 envs through encoder, value head, the A decoder iterations and the sampling).  Same contract as :meth:`act`;
+        ``states`` is ignored (pass None) and ``pos`` is not read (no timestep positional encoding).  Networks outside the kernel's shape
+        set (embed_dim 128, more than 8 agents or 4 blocks) take the kernel-by-kernel chain."""
+        if not self.ff:
+            raise ValueError("act_team_fused is the acting step of a memoryless network (memory_type='ff_sable'); a recurrent one acts "
+                             "through act_fused")
+        if not self.team_fused_supported():
+            return self.act(obs, pos, states, sample_keys, action_out, logp_out, value_out, mask=mask, value_only=value_only)
+        A, K, nb, v, wt = self.A, self.K, self.nb, self.v, self.wt
+        N = obs.shape[0]
+        kdev = sample_keys if torch.is_tensor(sample_keys) else None
+        need = 32 * ((N + 31) // 32) * A * (384 + 256 * nb)
+        args = (obs, mask, kdev, action_out, logp_out, value_out)
+
+        def table():   # 22 global pointers, then 18 per block (include/magpo.h)
+            glob = [obs, mask, kdev, v["enc.obs.norm.scale"], v["enc.obs.dense.kernel"], v["enc.ln.scale"], v["dec.act.kernel"], v["dec.ln.scale"],
+                    wt["vh0"], v["enc.head.dense0.bias"], v["enc.head.norm.scale"], v["enc.head.dense1.kernel"], v["enc.head.dense1.bias"],
+                    wt["h0"], v["dec.head.dense0.bias"], v["dec.head.norm.scale"], wt["h1"], v["dec.head.dense1.bias"],
+                    self.b.get(f"tf_scratch{need}", (need,)), action_out, logp_out, value_out]
+            blk = []
+            for k in range(nb):
+                e, d = f"enc.block{k}.", f"dec.block{k}."
+                blk += [wt[f"qkvg{k}"], wt[f"wo{k}"], v[e + "ln1.scale"], v[e + "ln2.scale"], v[e + "retn.gn.scale"], v[e + "retn.gn.bias"],
+                        wt[f"qkvg1{k}"], wt[f"wo1{k}"], v[d + "ln1.scale"], v[d + "retn1.gn.scale"], v[d + "retn1.gn.bias"],
+                        wt[f"q2{k}"], wt[f"kvg2{k}"], wt[f"wo2{k}"], v[d + "ln2.scale"], v[d + "ln3.scale"],
+                        v[d + "retn2.gn.scale"], v[d + "retn2.gn.bias"]]
+            return glob + blk
+
+        tab = self.ptr_table(("act_team", N) + tuple(None if t is None else t.data_ptr() for t in args), table)
+        gp, bp = tab[:22], tab[22:]
+        dims = np.array([N, A, K, self.F, nb, self.nh, self.hs, self.gs, 1 if value_only else 0, self.Fld], dtype=np.int32)
+        keys = None
+        if kdev is None and not value_only:
+            keys = np.ascontiguousarray(np.asarray(sample_keys, dtype=np.uint32).reshape(A, 2))
+        self.L.call("magpo_ff_sable_act", dims.ctypes.data, None if keys is None else keys.ctypes.data, gp.ctypes.data, int(gp.size),
+                    bp.ctypes.data, int(bp.size), need, self._st())
+
     # the reference's names for the two apply functions of the Sable network (rec_magpo.py:624-628)
-    get_actions = act_fused          # partial(sable_network.apply, method="get_actions"): execution  (apply = train_fwd: end of the file)
+    get_actions = act_fused        # partial(sable_network.apply, method="get_actions"): execution  (apply = train_fwd: end of the file)
 
     # ------------------------------------------------------------------ post-retention segment (contract of magpo_seg_post / magpo_seg_bwd)
     def _seg_fwd(self, tail, key, pfx, r, gp, ldg, res, s1, s2, pos, o, ope, R, w0_t=None, b0=None, out0=None, ld0=0, hs=None, hw=None,

@@ -56,7 +56,8 @@ def _owner(fn, cls, method: str, what: str):
         if f is None:
             break
     obj = getattr(f, "__self__", None)
-    names = {method} | ({"act_fused"} if method == "get_actions" else {"train_fwd", "seq_fwd"} if method == "apply" else set())
+    names = {method} | ({"act_fused"} if method == "get_actions" else {"train_fwd", "seq_fwd"} if method == "apply" else
+                        {"act_team_fused"} if method == "act" else set())   # (act_team_fused: the one-launch form of a memoryless network's act)
     if not isinstance(obj, cls) or getattr(f, "__name__", None) not in names:
         raise TypeError(
             f"get_learner_fn: {what} must be the bound method {cls.__name__}.{method} of a network / optimiser object (or a functools.wraps / "

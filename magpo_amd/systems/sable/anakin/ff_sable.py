@@ -87,7 +87,8 @@ def get_learner_fn(env, apply_fns, update_fn, config):
         apply_fns = (sable_action_select_fn, sable_apply_fn)     ff_sable.py:61   (execution / training)
         update_fn = the optimiser's update function              ff_sable.py:55
 
-    Under the rule of rec_sable.get_learner_fn: the callables must be the bound methods ``SableGuider.act`` (the stateless acting chain),
+    Under the rule of rec_sable.get_learner_fn: the callables must be the bound methods ``SableGuider.act`` (the stateless acting chain) or
+    ``SableGuider.act_team_fused`` (the same step in one launch),
     ``SableGuider.apply`` and ``ClipAdam.update`` of the objects that own the device buffers (or thin functools.wraps / functools.partial
     adaptors around them), and the loop CALLS exactly what it is given; anything else raises the ``TypeError`` of common._owner."""
     sable_action_select_fn, sable_apply_fn = apply_fns
@@ -121,13 +122,21 @@ def learner_setup(env, keys, config, device=None, rank: int = 0, world: int = 1)
                                 seed=np.asarray(net_key, np.uint32))
     optim = ClipAdam(sable_network, sysc)
     apply_fns = (sable_network.act, sable_network.apply)   # execution function, training function (ff_sable.py:396-401)
-    learn = get_learner_fn(env, apply_fns, optim.update, config)
+    # the rollout's action-select function follows Tuning.ff_sable_fused_act: the one-launch step, or the chain that is returned as the
+    # execution function either way
+    learn = get_learner_fn(env, (acting_fn(sable_network), apply_fns[1]), optim.update, config)
     return learn, apply_fns[0], setup_learner(learn, key, _snapshot_state, rank, world)
+
+
+def acting_fn(net: SableGuider) -> Callable:
+    """The acting step of a memoryless network under its tuning: ``act_team_fused`` (magpo_ff_sable_act, one launch) with
+    ``Tuning.ff_sable_fused_act`` on, else the kernel-by-kernel chain ``act``."""
+    return net.act_team_fused if net.tuning.ff_sable_fused_act else net.act
 
 
 def make_ff_sable_eval_act_fn(actor_apply_fn: Callable) -> Callable:
     """``EvalActFn(params, timestep, key, actor_state) -> (action, {})`` that executes the Sable network itself, statelessly
-    (ff_sable.py:475-486).  ``actor_apply_fn``: ``SableGuider.act`` of the network that evaluates (its own object, so that loading the
+    (ff_sable.py:475-486).  ``actor_apply_fn``: ``SableGuider.act`` or ``.act_team_fused`` (see ``acting_fn``) of the network that evaluates (its own object, so that loading the
     evaluated parameters does not touch the learner's).  As in the reference the action is always SAMPLED from ``key``.  Parameters are
     loaded when a DIFFERENT dict object arrives than the last one (see rec_sable.make_rec_sable_act_fn)."""
     net = _owner(actor_apply_fn, SableGuider, "act", "actor_apply_fn")
@@ -176,7 +185,7 @@ def run_experiment(_config) -> float:
     train_net = learn.learner.guider
     eval_net = SableGuider(train_net.A, train_net.K, train_net.F, device, obs_ld=train_net.Fld, embed_dim=train_net.EL, n_head=train_net.nh,
                            n_block=train_net.nb, memory_type="ff_sable", max_pos=train_net.npos, tuning=train_net.tuning)
-    return train_and_evaluate(config, env, eval_env, learn, learner_state, make_ff_sable_eval_act_fn(eval_net.act), key, key_e, device, rank, world,
+    return train_and_evaluate(config, env, eval_env, learn, learner_state, make_ff_sable_eval_act_fn(acting_fn(eval_net)), key, key_e, device, rank, world,
                               init_act_state=lambda batch: {}, eval_params=lambda state: state.params)
 
 

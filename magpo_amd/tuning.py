@@ -24,6 +24,9 @@ Environment variables are read HERE, once, when the default instance is built (A
     MAGPO_FF_FUSED_STEP=0|1     acting step of ff_ippo / ff_mappo: 1 = torso and head of both networks in one magpo_mlp_act_step launch (csrc/mlp_step.hip),
                                 0 = the composed chain of dense kernels per network.  Same function, same fp32 summation order.
                                 Default: see Tuning.ff_fused_step
+    MAGPO_FF_SABLE_FUSED_ACT=0|1  acting step of ff_sable: 1 = encoder, value head, the A decoder iterations and the sampling in one magpo_ff_sable_act
+                                launch (csrc/ff_sable_act.hip, SableGuider.act_team_fused), 0 = the kernel-by-kernel chain SableGuider.act.  Same function;
+                                the one launch is the more accurate and, as measured, the slower of the two: default 0
 """
 from __future__ import annotations
 
@@ -42,6 +45,7 @@ class Tuning:
     act_envs_per_wave: int = 0    # magpo_sable_act dims[11]
     ppo_fused_step: bool = True   # critic.step_pair: magpo_gru_cell_step (True) or the composed step of each network (False)
     ff_fused_step: bool = True    # ff_nets.act_pair: magpo_mlp_act_step (True) or the composed dense chain of each network (False)
+    ff_sable_fused_act: bool = False  # ff_sable acting step: SableGuider.act_team_fused / magpo_ff_sable_act (True) or the chain SableGuider.act (False)
 
     @classmethod
     def from_env(cls, env=None) -> "Tuning":
@@ -56,4 +60,6 @@ class Tuning:
         t.act_envs_per_wave = int(e["MAGPO_ACT_EPW"]) if e.get("MAGPO_ACT_EPW") in ("4", "8", "16") else 0
         t.ppo_fused_step = e["MAGPO_PPO_FUSED_STEP"] == "1" if e.get("MAGPO_PPO_FUSED_STEP") in ("0", "1") else cls().ppo_fused_step
         t.ff_fused_step = e["MAGPO_FF_FUSED_STEP"] == "1" if e.get("MAGPO_FF_FUSED_STEP") in ("0", "1") else cls().ff_fused_step
+        t.ff_sable_fused_act = (e["MAGPO_FF_SABLE_FUSED_ACT"] == "1" if e.get("MAGPO_FF_SABLE_FUSED_ACT") in ("0", "1")
+                                else cls().ff_sable_fused_act)
         return t

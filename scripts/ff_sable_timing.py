@@ -1,11 +1,14 @@
 """Acting-step, update-step and retention-kernel times of the memoryless Sable system (ff_sable) on the bench's headline shape: CoordSum-4ag,
 16 384 envs, 128-step rollout, 4 epochs x 2 minibatches, configs/network/ff_retention.yaml defaults (embed_dim 64, 1 head, 1 block).
 
-    python scripts/ff_sable_timing.py --what act          # one acting step (SableGuider.act, the kernel-by-kernel chain on team kernels)
-    python scripts/ff_sable_timing.py --what update       # one ff_sable update step
+    python scripts/ff_sable_timing.py --what act          # one acting step both ways, one child process each: --fused 0 (SableGuider.act, the
+                                                          # kernel-by-kernel chain on team kernels) and --fused 1 (act_team_fused: magpo_ff_sable_act)
+    python scripts/ff_sable_timing.py --what act --fused 1 --num-envs 4096     # one of them, in this process
+    python scripts/ff_sable_timing.py --what act --shape 8x15                  # 8 agents, 15 actions, two blocks
+    python scripts/ff_sable_timing.py --what update --fused 0|1                # one ff_sable update step
     python scripts/ff_sable_timing.py --what rec-update   # the same update step of rec_sable, for scale
     python scripts/ff_sable_timing.py --what kernels      # team kernels against the chunk kernels run as T = 1 sequences, 65 536 teams of 4
-    python scripts/ff_sable_timing.py --what all --out profiles/ff_sable_step_time.json   # the four above, one child process each
+    python scripts/ff_sable_timing.py --what all --out profiles/ff_sable_step_time.json   # all of the above, one child process each
 
 Each measurement is its own process under its own time limit.  HIP events after warm-up: the acting step and the kernels are medians over
 --steps launches, the update steps one event pair per step as in bench.py (two untimed set-up steps for workspaces and the rollout graph
@@ -42,29 +45,40 @@ def _median_us(fn, steps, warmup):
     return us, round(sorted(us)[len(us) // 2], 1)
 
 
-def learner(N, rec):
+SHAPES = {"4ag": (CFG, 1), "8x15": (dict(num_agents=8, num_actions=15, time_limit=100, maxval=100), 2)}   # env, n_block
+
+
+def learner(N, rec, fused=None, shape="4ag"):
+    cfg, nb = SHAPES[shape]
     if rec:
         from magpo_amd.sable_learner import SableLearner
-        l = SableLearner(CoordSumConfig(**CFG), N, SystemConfig(), "cuda", net_seed=0)
+        l = SableLearner(CoordSumConfig(**cfg), N, SystemConfig(), "cuda", net_seed=0, n_block=nb)
     else:
         from magpo_amd.ff_sable_learner import FfSableLearner
-        l = FfSableLearner(CoordSumConfig(**CFG), N, SystemConfig(), "cuda", net_seed=0)
+        from magpo_amd.tuning import Tuning
+        t = Tuning.from_env()
+        if fused is not None:
+            t.ff_sable_fused_act = bool(fused)
+        l = FfSableLearner(CoordSumConfig(**cfg), N, SystemConfig(), "cuda", net_seed=0, n_block=nb, tuning=t)
     l.setup(host_split(prng_key(42), 3)[0])
     return l
 
 
-def time_act(N, steps, warmup):
-    l = learner(N, False)
+def time_act(N, steps, warmup, fused, shape):
+    """One acting step as the rollout makes it: the learner's action-select function (Tuning.ff_sable_fused_act: magpo_ff_sable_act, or the
+    chain SableGuider.act)."""
+    l = learner(N, False, fused, shape)
     g, tr = l.groups[0], l.groups[0].traj
     l._rollout_keys(g)
     obs = l._net_view(tr["obs"][0])
-    us, med = _median_us(lambda: l.guider.act(obs, tr["step_count"][0], None, g.keys_host[0], tr["action"][0], tr["log_prob"][0], tr["value"][0]),
+    act = l.sable_action_select_fn
+    us, med = _median_us(lambda: act(obs, tr["step_count"][0], None, g.keys_host[0], tr["action"][0], tr["log_prob"][0], tr["value"][0]),
                          steps, warmup)
-    return dict(us_per_step=[round(x, 1) for x in us[:8]], median_us=med)
+    return dict(shape=shape, fused_act=bool(l.tuning.ff_sable_fused_act), method=act.__name__, us_per_step=[round(x, 1) for x in us[:8]], median_us=med)
 
 
-def time_update(N, steps, warmup, rec):
-    l = learner(N, rec)
+def time_update(N, steps, warmup, rec, fused=None, shape="4ag"):
+    l = learner(N, rec, fused, shape)
     for _ in range(2 + warmup):
         l.update_step()
     torch.cuda.synchronize()
@@ -77,7 +91,7 @@ def time_update(N, steps, warmup, rec):
         e1.synchronize()
         ms.append(e0.elapsed_time(e1))
     med = sorted(ms)[len(ms) // 2]
-    return dict(system="rec_sable" if rec else "ff_sable", ms_per_update_step=[round(x, 2) for x in ms], median_ms=round(med, 2),
+    return dict(system="rec_sable" if rec else "ff_sable", shape=shape, fused_act=None if rec else bool(l.tuning.ff_sable_fused_act), ms_per_update_step=[round(x, 2) for x in ms], median_ms=round(med, 2),
                 env_steps_per_second=round(l.T * N / (med * 1e-3)), graph=l.groups[0].graph is not None,
                 peak_hbm_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))
 
@@ -116,12 +130,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--child-timeout", type=int, default=240)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--fused", type=int, choices=(0, 1), default=None,
+                    help="ff_sable acting step: 1 = magpo_ff_sable_act, 0 = the chain; default: --what act measures both (one child process each), "
+                         "update follows the environment (MAGPO_FF_SABLE_FUSED_ACT) or the default")
+    ap.add_argument("--shape", choices=sorted(SHAPES), default="4ag", help="4ag: CoordSum-4ag, one block; 8x15: 8 agents, 15 actions, two blocks")
     a = ap.parse_args()
-    if a.what == "all":   # one fresh child process per measurement, each under its own time limit
+    both = a.what == "act" and a.fused is None
+    if a.what == "all" or both:   # one fresh child process per measurement, each under its own time limit
         lines = []
-        for what in ("act", "kernels", "update", "rec-update"):
-            r = subprocess.run(["timeout", "-k", "10", str(a.child_timeout), sys.executable, os.path.abspath(__file__), "--what", what, "--num-envs",
-                                str(a.num_envs)], capture_output=True, text=True)
+        jobs = [("act", "0"), ("act", "1")] if both else [("act", "0"), ("act", "1"), ("kernels", None), ("update", "0"), ("update", "1"), ("rec-update", None)]
+        for what, fused in jobs:
+            cmd = ["timeout", "-k", "10", str(a.child_timeout), sys.executable, os.path.abspath(__file__), "--what", what, "--num-envs", str(a.num_envs),
+                   "--shape", a.shape] + ([] if fused is None else ["--fused", fused])
+            for opt, val in (("--steps", a.steps), ("--warmup", a.warmup)):
+                if both and val is not None:
+                    cmd += [opt, str(val)]
+            r = subprocess.run(cmd, capture_output=True, text=True)
             if r.returncode != 0:   # nothing more is started on the GPU after a failed measurement
                 sys.exit(f"{what} failed ({r.returncode}):\n{r.stderr[-2000:]}")
             lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
@@ -129,11 +153,11 @@ def main():
         text = json.dumps(dict(workload=WORKLOAD, num_envs=a.num_envs, measurements=lines), indent=1)
     else:
         if a.what == "act":
-            res = time_act(a.num_envs, a.steps or 100, 10 if a.warmup is None else a.warmup)
+            res = time_act(a.num_envs, a.steps or 100, 10 if a.warmup is None else a.warmup, a.fused, a.shape)
         elif a.what == "kernels":
             res = time_kernels(65536, 4, a.steps or 100, 10 if a.warmup is None else a.warmup)
         else:
-            res = time_update(a.num_envs, a.steps or 3, 1 if a.warmup is None else a.warmup, a.what == "rec-update")
+            res = time_update(a.num_envs, a.steps or 3, 1 if a.warmup is None else a.warmup, a.what == "rec-update", a.fused, a.shape)
         text = json.dumps(dict(workload=WORKLOAD, what=a.what, num_envs=a.num_envs, device=torch.cuda.get_device_name(0), **res))
         print(text)
     if a.out:
