@@ -148,6 +148,14 @@ int magpo_linear_pro(int pro, const float* a, long lda, const float* y, long ldy
 long magpo_wgrad_workspace_floats(int KIN, int NOUT, int G);
 int magpo_wgrad(const float* X, int ldx, const float* dY, int ldy, long R, int KIN, int krows, int NOUT, float* dW,
                 float* db, float* workspace, int G, float scale, int accumulate, int variant, magpo_stream_t stream);
+/* Backward of a narrow dense layer in one launch: dW[KIN][NOUT] (+ db[NOUT], nullable) = X^T dY and dX[R][KIN] = dY W^T from one pass over
+ * X and dY.  KIN in {64, 128}, 1 <= NOUT <= 64; W in its natural [KIN][NOUT] layout (contiguous); ldx, ldy, lddx, ldmask multiples of 4
+ * (ldy >= NOUT: columns >= NOUT of dY are never used); X and dY 16-byte aligned (read as float4).  act 0: mask null; act 4: dX = mask > 0 ? dX : 0 (mask [R][KIN], stride ldmask; may
+ * be X itself).  dW / db leave as per-workgroup slabs in workspace (>= magpo_wgrad_workspace_floats(KIN, NOUT, G) floats) folded in a fixed
+ * order: two launches give the same bits.  Any other argument combination is MAGPO_EINVAL before a pointer is touched. */
+int magpo_dense_bwd(const float* X, int ldx, const float* dY, int ldy, const float* W, const float* mask, int ldmask,
+                    float* dX, int lddx, long R, int KIN, int NOUT, float* dW, float* db, float* workspace, int G, int act,
+                    magpo_stream_t stream);
 int magpo_reduce_slabs(const float* slab, float* out, int G, long P, long stride, float scale, int accumulate,
                        magpo_stream_t stream);
 int magpo_transpose_pad(const float* W, float* Wt, int K, int N, int Npad, magpo_stream_t stream);

@@ -198,10 +198,16 @@ class GruActor(TorsoNet):
         sv = self._saved
         R, nseq, T, obs, dones = sv["R"], sv["nseq"], sv["T"], sv["obs"], sv["dones"]
         post, pre, Dq, Dp = sv["post"], sv["pre"], self.Dpost, self.Dpre
-        self.wgrad(post[-1][3], Dq, dlogits, 64, R, Dq, K, gv["head.kernel"], gv["head.bias"])
         dy = b.get("g_post_dy", (R, Dq))
-        # dy = dlogits @ W_head^T, masked by the last post-torso layer's activation (fused epilogue: act 4 / 6 take it as the mask argument)
-        self._dx(dlogits, 64, self.wt["head_nat_pad"], 64, Dq, R, dy, self.post_spec, len(post) - 1, post[-1])
+        # dy = dlogits @ W_head^T, masked by the last post-torso layer's activation (fused epilogue: act 4 / 6 take it as the mask argument).
+        # A ReLU layer without LayerNorm of width 64 / 128: head gradient and dy from one pass (dense_bwd; the layer's output is X and the mask)
+        last = post[-1]
+        if last[4] is None and self.post_spec.act(len(post) - 1) == 1:
+            self.dense_bwd(last[3], Dq, dlogits, 64, v["head.kernel"], dy, Dq, R, Dq, K, gv["head.kernel"], gv["head.bias"], act=4, mask=last[3],
+                           lin_W=self.wt["head_nat_pad"], lin_K=64)
+        else:
+            self.wgrad(last[3], Dq, dlogits, 64, R, Dq, K, gv["head.kernel"], gv["head.bias"])
+            self._dx(dlogits, 64, self.wt["head_nat_pad"], 64, Dq, R, dy, self.post_spec, len(post) - 1, last)
         dz0 = self._torso_bwd("post", self.post_spec, post, dy)
         dhs = b.get("g_dhs", (R, H))
         self.lin(dz0, self.post_spec.layer_sizes[0], v["post.kernel"], None, dhs, H, R, self.post_spec.layer_sizes[0], H)

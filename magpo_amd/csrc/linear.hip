@@ -6,6 +6,9 @@
 //                   projections: sable_network.py:93-109,258-284, retention.py:73-75,294, base.py:175-181).
 //   k_wgrad<NB>   : dW[KIN,NOUT] partial sums = X^T dY per workgroup slab (+ column sums of dY for
 //                   the bias), reduced in fixed order by k_reduce_slabs (bit-stable reruns).
+//   k_dense_bwd<KT, NT, MASK> : the backward of a narrow layer (KIN 64 / 128, NOUT <= 64) in one pass over X and dY: the dW / db slabs
+//                   AND dX = dY @ W^T (optionally masked by aux > 0, aux may be X), both from one 64-row tile of X and dY in LDS
+//                   (magpo_dense_bwd; replaces a k_wgrad<1> + k_linear_lds pair from 16 384 rows on).
 //
 // Tile of k_linear_lds: 32 rows x (32 NW) columns per workgroup, one 32x32 accumulator per wave.  A wave keeps the weight
 // fragments of its 32 columns in VGPRs (each lane owns one output column and half of its k's) for the whole persistent loop;
@@ -1007,6 +1010,225 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_full_g(const float* __restrict
   }
 }
 
+// Backward of a NARROW dense layer in one pass: dW[KIN][NOUT] (+ db) = X^T dY as per-workgroup slabs AND dX = dY W^T (optionally masked:
+// dX = aux > 0 ? dX : 0, act 4 of magpo_linear), KIN = 64 KT, NOUT <= 32 NT.  The pair k_wgrad + k_linear_lds reads dY twice (and X twice
+// when X is the ReLU mask); here the 64-row tiles of X [64][KIN] and dY [64][32 NT] go from HBM to LDS once and serve both GEMMs and the mask.
+//   loads  : uniform tile base + per-thread 32-bit offset (rows past R re-read the last valid row and are zeroed when stashed; columns
+//            >= NOUT of dY are zeroed on the loaded values, the float4 column is clamped so that nothing past a row's NOUT columns, rounded
+//            up to 4, is addressed); the next tile's loads are issued one per MFMA step of the dW loop.
+//   Every output has the BITS of the pair it replaces (k_wgrad<1> slabs + k_reduce_slabs; k_linear_lds with the natural weights padded to 64
+//   columns), because every sum runs over the same terms in the same order:
+//   dW     : 2 KT x NT blocks of 32 x 32, each over all 64 rows of a tile with k-step s = rows (s, 32 + s) as in k_wgrad, slabs over the same
+//            tiles.  64 x (33..64): wave = (k block, column block); 128 x (1..32): wave = k block; 128 x (33..64): wave = (two k blocks,
+//            column block); 64 x (1..32) has two blocks only: waves 0 and 2 (1 and 3 idle here, wave 1 takes the bias sums).  Bias: the tile's
+//            column sums over its 64 rows from LDS, then added to the slab's sum, as k_wgrad does.
+//   dX     : wave = (row half, column half of KIN), one 32-column block at a time; the contraction runs over 64 columns in k_linear_lds's
+//            order (lane half h owns columns 32 h + 4 u + e).  NT == 2: the W fragments (32 KT registers) stay in VGPRs.  NT == 1: columns
+//            32..63 are the zero padding, so the upper lane half multiplies by zero; the lower half reads its 32 weights per block as
+//            ds_read_b128 from an LDS image of W ([KIN + 1][36], last row zero for the upper half) -- no weight registers.  dY rows are
+//            ds_read_b128 from the padded tile ([64][32 NT + 4]: conflict-free), stores as k_linear_lds.
+//   MASK   : 0 none; 1 aux read from global memory (16 loads per block, the pattern of the stores); 2 aux is X itself (same pointer and
+//            stride): read from the X tile in LDS (column-consecutive).
+// 128 x (33..64) needs 64 registers of W fragments: one workgroup per CU there (no production layer has that shape), two elsewhere.
+template <int KT, int NT, int MASK>
+__global__ __launch_bounds__(256, KT * NT == 4 ? 1 : 2) void k_dense_bwd(const float* __restrict__ X, int ldx, const float* __restrict__ dY, int ldy,
+                                                      const float* __restrict__ W, const float* __restrict__ aux, int ldaux,
+                                                      float* __restrict__ dX, int lddx, int R, int NOUT, float* __restrict__ slab,
+                                                      float* __restrict__ bias_slab) {
+  constexpr int KIN = 64 * KT, NC = 32 * NT, LDX = KIN, LDY = NC + LDP;
+  constexpr int TX = KIN / 4, RPX = 256 / TX, NLX = 64 / RPX;   // X: TX threads per row, RPX rows per pass, NLX passes
+  constexpr int TY = NC / 4, RPY = 256 / TY, NLY = 64 / RPY;    // dY likewise
+  constexpr bool HALF = KT == 1 && NT == 1;                     // dW: two blocks only, two of the four waves carry them
+  constexpr int KW = KT * NT == 4 ? 2 : 1;                      // dW accumulator tiles per wave
+  constexpr int NSW = 32;                                       // dW k-steps (two rows each) per tile
+  constexpr bool WL = NT == 1;                                  // dX weights from an LDS image
+  constexpr int LDW = 32 + LDP, NU = 8;                         // NU float4 per lane and dX block: 32 contraction columns per lane half
+  static_assert(NLX + NLY <= NSW, "one load of the next tile per dW step");
+  __shared__ __align__(16) float xs[64 * LDX];
+  __shared__ __align__(16) float ys[64 * LDY];
+  __shared__ __align__(16) float wl[WL ? (KIN + 1) * LDW : 4];
+  const int tid = threadIdx.x, lane = tid & 63, lr = lane & 31, h = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // in a scalar register: what follows from it (row bases, LDS offsets) stays off the VALU
+  const int wa = wave >> 1, wb = wave & 1;    // dX: (row half, column half)
+  const int kb0 = (KT == 2 && NT == 1) ? wave : KW * wa, cbw = NT == 2 ? wb : 0;   // dW: first k block, column block
+  const int g = blockIdx.x, G = gridDim.x;
+  const int ntiles = (R + 63) >> 6;
+  // W fragments of dX (NT == 2): lane (lr, h) holds W[32 (KT wb + j) + lr][32 h + 4 u + e]
+  float4 wf[WL ? 1 : KT][WL ? 1 : NU];
+  if constexpr (!WL) {
+#pragma unroll
+    for (int j = 0; j < KT; ++j) {
+      const float* wrow = W + (long)(32 * (KT * wb + j) + lr) * NOUT;
+#pragma unroll
+      for (int u = 0; u < NU; ++u) {
+        const int c = 32 * h + 4 * u;
+        wf[j][u].x = c + 0 < NOUT ? wrow[c + 0] : 0.f;
+        wf[j][u].y = c + 1 < NOUT ? wrow[c + 1] : 0.f;
+        wf[j][u].z = c + 2 < NOUT ? wrow[c + 2] : 0.f;
+        wf[j][u].w = c + 3 < NOUT ? wrow[c + 3] : 0.f;
+      }
+    }
+  } else {   // image [KIN + 1][LDW]: W's columns zero-padded, row KIN all zero (first read after the first tile's second barrier)
+    for (int idx = tid; idx < (KIN + 1) * LDW; idx += 256) {
+      const int k = idx / LDW, c = idx - k * LDW;
+      wl[idx] = (k < KIN && c < NOUT) ? W[(long)k * NOUT + c] : 0.f;
+    }
+  }
+  f32x16 accw[KW];
+#pragma unroll
+  for (int kt = 0; kt < KW; ++kt)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) accw[kt][i] = 0.f;
+  float bsum = 0.f;
+  const bool dwa = !HALF || wb == 0;            // this wave carries dW blocks
+  const int bt = tid - (HALF ? 64 : 0);         // bias column of this thread (one wave, or two for 64 columns)
+  const bool do_bias = bias_slab != nullptr && bt >= 0 && bt < NC;
+  const unsigned xr_ = (unsigned)(tid / TX), xc_ = 4u * (unsigned)(tid % TX);
+  const unsigned yr_ = (unsigned)(tid / TY), yc_ = 4u * (unsigned)(tid % TY);
+  const unsigned ycl = min(yc_, 4u * ((unsigned)(NOUT - 1) >> 2));   // clamped float4 column: never past the row's NOUT columns rounded up to 4
+  const bool yk0 = (int)yc_ + 0 < NOUT, yk1 = (int)yc_ + 1 < NOUT, yk2 = (int)yc_ + 2 < NOUT, yk3 = (int)yc_ + 3 < NOUT;
+  float* xsw = xs + xr_ * LDX + xc_;
+  float* ysw = ys + yr_ * LDY + yc_;
+  // dX / mask element of accumulator register i: (scalar row pointer of tile row (i & 3) + 8 (i >> 2))[per-thread 32-bit offset]
+  const unsigned so = (unsigned)(32 * wa + 4 * h) * (unsigned)lddx + (unsigned)(32 * KT * wb + lr);
+  const unsigned mo = (unsigned)(32 * wa + 4 * h) * (unsigned)ldaux + (unsigned)(32 * KT * wb + lr);
+  float4 nxx[NLX], nxy[NLY];
+#define DB_LOADX(J, XB, RMAX) nxx[J] = *reinterpret_cast<const float4*>((XB) + (min(xr_ + (unsigned)(RPX * (J)), (RMAX)) * (unsigned)ldx + xc_))
+#define DB_LOADY(J, YB, RMAX) nxy[J] = *reinterpret_cast<const float4*>((YB) + (min(yr_ + (unsigned)(RPY * (J)), (RMAX)) * (unsigned)ldy + ycl))
+  {
+    const long r0 = (long)min(g, ntiles - 1) * 64;
+    const float* xb = X + r0 * ldx;
+    const float* yb = dY + r0 * ldy;
+    const unsigned rmax = (unsigned)min(63L, (long)R - 1 - r0);
+#pragma unroll
+    for (int j = 0; j < NLX; ++j) { DB_LOADX(j, xb, rmax); }
+#pragma unroll
+    for (int j = 0; j < NLY; ++j) { DB_LOADY(j, yb, rmax); }
+  }
+  const int tok0 = 32 * h;
+  const float* xrd = xs + tok0 * LDX + 32 * kb0 + lr;
+  const float* yrd = ys + tok0 * LDY + 32 * cbw + lr;
+  const float* ard = ys + (32 * wa + lr) * LDY + (WL ? 0 : 32 * h);
+  for (int tile = g; tile < ntiles; tile += G) {
+    const long row0 = (long)tile * 64;
+    const long r0n = (long)min(tile + G, ntiles - 1) * 64;
+    const float* xbn = X + r0n * ldx;
+    const float* ybn = dY + r0n * ldy;
+    const unsigned rmaxn = (unsigned)min(63L, (long)R - 1 - r0n);
+    const int rleft = (int)min(64L, (long)R - row0);   // valid rows of this tile
+    __syncthreads();          // the previous tile's LDS reads (MFMA operands, mask) are done
+#pragma unroll
+    for (int j = 0; j < NLX; ++j) {   // component-wise selects keep the arrays in registers
+      const float4 v = nxx[j];
+      const bool ok = (int)xr_ + RPX * j < rleft;
+      *reinterpret_cast<float4*>(xsw + RPX * j * LDX) = make_float4(ok ? v.x : 0.f, ok ? v.y : 0.f, ok ? v.z : 0.f, ok ? v.w : 0.f);
+    }
+#pragma unroll
+    for (int j = 0; j < NLY; ++j) {
+      const float4 v = nxy[j];
+      const bool ok = (int)yr_ + RPY * j < rleft;
+      const float4 z = make_float4(ok && yk0 ? v.x : 0.f, ok && yk1 ? v.y : 0.f, ok && yk2 ? v.z : 0.f, ok && yk3 ? v.w : 0.f);
+      *reinterpret_cast<float4*>(ysw + RPY * j * LDY) = z;
+    }
+    __syncthreads();
+    // ---- dW += X^T dY; operands one k-step ahead, one load of the next tile per step
+    if (dwa) {
+      float av[2][KW], bv[2];
+#pragma unroll
+      for (int kt = 0; kt < KW; ++kt) av[0][kt] = xrd[32 * kt];
+      bv[0] = yrd[0];
+#pragma unroll
+      for (int s = 0; s < NSW; ++s) {
+        if (s + 1 < NSW) {
+#pragma unroll
+          for (int kt = 0; kt < KW; ++kt) av[(s + 1) & 1][kt] = xrd[(s + 1) * LDX + 32 * kt];
+          bv[(s + 1) & 1] = yrd[(s + 1) * LDY];
+        }
+#pragma unroll
+        for (int kt = 0; kt < KW; ++kt) accw[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s & 1][kt], bv[s & 1], accw[kt], 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < NLX; ++j)
+          if (j == s) { DB_LOADX(j, xbn, rmaxn); }
+#pragma unroll
+        for (int j = 0; j < NLY; ++j)
+          if (NLX + j == s) { DB_LOADY(j, ybn, rmaxn); }
+      }
+    } else {   // (64 x (1..32): waves 1 and 3) only the next tile's loads
+#pragma unroll
+      for (int j = 0; j < NLX; ++j) { DB_LOADX(j, xbn, rmaxn); }
+#pragma unroll
+      for (int j = 0; j < NLY; ++j) { DB_LOADY(j, ybn, rmaxn); }
+    }
+    if (do_bias) {   // the tile's column sum first, then the slab's: k_wgrad's order
+      float sb = 0.f;
+#pragma unroll 8
+      for (int r = 0; r < 64; ++r) sb += ys[r * LDY + bt];
+      bsum += sb;
+    }
+    // ---- dX tile = dY tile W^T, one 32-column block at a time (one accumulator tile live).  Accumulator register i of lane (lr, h) is
+    // tile row 32 wa + (i & 3) + 8 (i >> 2) + 4 h, column 32 (KT wb + j) + lr; row addresses are scalar + a per-thread 32-bit offset.
+    const bool full = rleft == 64;
+#pragma unroll
+    for (int j = 0; j < KT; ++j) {
+      f32x16 accx;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) accx[i] = 0.f;
+      const float* wrd = wl + (WL ? (h ? KIN : 32 * (KT * wb + j) + lr) * LDW : 0);   // upper lane half: the zero row
+#pragma unroll
+      for (int u = 0; u < NU; ++u) {
+        const float4 a4 = *reinterpret_cast<const float4*>(ard + 4 * u);
+        float4 w4;
+        if constexpr (WL) w4 = *reinterpret_cast<const float4*>(wrd + 4 * u);
+        else w4 = wf[j][u];
+        accx = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, w4.x, accx, 0, 0, 0);
+        accx = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, w4.y, accx, 0, 0, 0);
+        accx = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, w4.z, accx, 0, 0, 0);
+        accx = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, w4.w, accx, 0, 0, 0);
+      }
+      const int cb = 32 * (KT * wb + j);
+      float* dxt = dX + row0 * lddx + 32 * j;
+      const float* mt = MASK == 1 ? aux + row0 * ldaux + 32 * j : nullptr;
+#define DB_TR(I) (((I) & 3) + 8 * ((I) >> 2))
+      if (full) {
+        if constexpr (MASK != 0) {
+          float mk[16];
+#pragma unroll
+          for (int i = 0; i < 16; ++i) mk[i] = MASK == 2 ? xs[(32 * wa + DB_TR(i) + 4 * h) * LDX + cb + lr] : (mt + DB_TR(i) * ldaux)[mo];
+#pragma unroll
+          for (int i = 0; i < 16; ++i) (dxt + DB_TR(i) * lddx)[so] = mk[i] > 0.f ? accx[i] : 0.f;
+        } else {
+#pragma unroll
+          for (int i = 0; i < 16; ++i) (dxt + DB_TR(i) * lddx)[so] = accx[i];
+        }
+      } else {   // the ragged last tile
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          if (32 * wa + DB_TR(i) + 4 * h < rleft) {
+            float v = accx[i];
+            if constexpr (MASK != 0) v = (MASK == 2 ? xs[(32 * wa + DB_TR(i) + 4 * h) * LDX + cb + lr] : (mt + DB_TR(i) * ldaux)[mo]) > 0.f ? v : 0.f;
+            (dxt + DB_TR(i) * lddx)[so] = v;
+          }
+        }
+      }
+#undef DB_TR
+    }
+  }
+#undef DB_LOADX
+#undef DB_LOADY
+  // ---- slabs
+  if (dwa) {
+    const int n = 32 * cbw + lr;
+    float* out = slab + (long)g * KIN * NOUT;
+    if (n < NOUT) {
+#pragma unroll
+      for (int kt = 0; kt < KW; ++kt)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) out[(long)(32 * (kb0 + kt) + (i & 3) + 8 * (i >> 2) + 4 * h) * NOUT + n] = accw[kt][i];
+    }
+  }
+  if (do_bias && bt < NOUT) bias_slab[(long)g * NOUT + bt] = bsum;
+}
+
 }  // namespace magpo
 
 using namespace magpo;
@@ -1132,6 +1354,42 @@ extern "C" int magpo_wgrad(const float* X, int ldx, const float* dY, int ldy, lo
   hipLaunchKernelGGL(k_reduce_slabs, dim3((unsigned)((P + 63) / 64)), dim3(1024), 0, stream, workspace, dW, G, P, (long)KIN * NOUT, scale, accumulate);
   if (db) hipLaunchKernelGGL(k_reduce_slabs, dim3((NOUT + 63) / 64), dim3(1024), 0, stream, bias_slab(), db, G, (long)NOUT, (long)NOUT, scale, accumulate);
   return check_launch("magpo_wgrad");
+}
+
+// Narrow dense-layer backward in one launch (k_dense_bwd): dW[KIN][NOUT] (+ db) = X^T dY and dX[R][KIN] = dY W^T, W in its natural
+// [KIN][NOUT] layout (contiguous); act 4: dX = mask > 0 ? dX : 0 (mask may be X itself).  workspace >= magpo_wgrad_workspace_floats.
+extern "C" int magpo_dense_bwd(const float* X, int ldx, const float* dY, int ldy, const float* W, const float* mask, int ldmask,
+                               float* dX, int lddx, long R, int KIN, int NOUT, float* dW, float* db, float* workspace, int G, int act,
+                               hipStream_t stream) {
+  if (KIN != 64 && KIN != 128) { set_error("magpo_dense_bwd: KIN must be 64 or 128"); return MAGPO_EINVAL; }
+  if (NOUT < 1 || NOUT > 64) { set_error("magpo_dense_bwd: NOUT must be in [1, 64]"); return MAGPO_EINVAL; }
+  if ((ldx & 3) || (ldy & 3) || (lddx & 3) || ldx < KIN || lddx < KIN || ldy < NOUT) {
+    set_error("magpo_dense_bwd: ldx, ldy, lddx must be multiples of 4 and cover KIN / NOUT / KIN columns"); return MAGPO_EINVAL;
+  }
+  if (act != ACT_NONE && act != ACT_MASKPOS) { set_error("magpo_dense_bwd: act must be 0 or 4"); return MAGPO_EINVAL; }
+  if (act == ACT_MASKPOS && !mask) { set_error("magpo_dense_bwd: act 4 needs the mask tensor"); return MAGPO_EINVAL; }
+  if (act == ACT_NONE && mask) { set_error("magpo_dense_bwd: the mask argument must be null for act 0"); return MAGPO_EINVAL; }
+  if (mask && ((ldmask & 3) || ldmask < KIN)) { set_error("magpo_dense_bwd: ldmask must be a multiple of 4 and cover KIN columns"); return MAGPO_EINVAL; }
+  if (R < 1 || R > 0x7fffffffL - 64 || G < 1) { set_error("magpo_dense_bwd: R must be in [1, 2^31 - 65], G positive"); return MAGPO_EINVAL; }
+  // rows of X and dY are read as float4 (dX and a separate mask go element by element)
+  if (((uintptr_t)X | (uintptr_t)dY) & 15) { set_error("magpo_dense_bwd: X and dY must be 16-byte aligned"); return MAGPO_EINVAL; }
+  if (G > 512) G = 512;   // two resident workgroups per CU
+  if (G > (R + 63) / 64) G = (int)((R + 63) / 64);
+  float* bias_slab = db ? workspace + (long)G * KIN * NOUT : nullptr;
+  const int m = act != ACT_MASKPOS ? 0 : (mask == X && ldmask == ldx) ? 2 : 1;   // 2: the mask is the X tile already in LDS
+  const bool k2 = KIN == 128, n2 = NOUT > 32;
+  decltype(&k_dense_bwd<1, 1, 0>) k;
+#define DB_PICK(KT_, NT_) (m == 0 ? k_dense_bwd<KT_, NT_, 0> : m == 1 ? k_dense_bwd<KT_, NT_, 1> : k_dense_bwd<KT_, NT_, 2>)
+  if (!k2 && !n2) k = DB_PICK(1, 1);
+  else if (!k2) k = DB_PICK(1, 2);
+  else if (!n2) k = DB_PICK(2, 1);
+  else k = DB_PICK(2, 2);
+#undef DB_PICK
+  hipLaunchKernelGGL(k, dim3(G), dim3(256), 0, stream, X, ldx, dY, ldy, W, mask, ldmask, dX, lddx, (int)R, NOUT, workspace, bias_slab);
+  const long P = (long)KIN * NOUT;
+  hipLaunchKernelGGL(k_reduce_slabs, dim3((unsigned)((P + 63) / 64)), dim3(1024), 0, stream, workspace, dW, G, P, P, 1.0f, 0);
+  if (db) hipLaunchKernelGGL(k_reduce_slabs, dim3(1), dim3(1024), 0, stream, bias_slab, db, G, (long)NOUT, (long)NOUT, 1.0f, 0);
+  return check_launch("magpo_dense_bwd");
 }
 
 extern "C" int magpo_reduce_slabs(const float* slab, float* out, int G, long P, long stride, float scale, int accumulate, hipStream_t stream) {

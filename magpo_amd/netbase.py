@@ -86,6 +86,28 @@ class NetBase:
         with torch.cuda.stream(side):
             self.L.call("magpo_wgrad", X, ldx, dY, ldy, R, KIN, krows or KIN, NOUT, dW, db, self.wg_ws, self._groups(R), 1.0, 0, self.tuning.wgrad_variant, self._st())
 
+    def _dense_bwd_fused(self, R, KIN, NOUT, act=0):
+        """Whether ``dense_bwd`` serves this layer with the one-launch kernel: a shape magpo_dense_bwd takes, and a minibatch of at least
+        ``tuning.dense_bwd_min_rows`` rows (below it the launch sequence is the pair's, unchanged)."""
+        return KIN in (64, 128) and 1 <= NOUT <= 64 and act in (0, 4) and R >= self.tuning.dense_bwd_min_rows
+
+    def dense_bwd(self, X, ldx, dY, ldy, W_nat, dX, lddx, R, KIN, NOUT, dW, db=None, act=0, mask=None, lin_W=None, lin_K=None):
+        """Backward of a narrow dense layer: dW [KIN, NOUT] (+ db) = X^T dY and dX [R, KIN] = dY W_nat^T (act 4: masked by ``mask`` > 0, which
+        may be X).  ``mask`` has dX's row stride ``lddx`` (magpo_linear's convention for act 4, which the pair below relies on; with
+        mask = X that means ldx == lddx, and the kernel then reads the mask from its X tile).  One magpo_dense_bwd launch (csrc/linear.hip:
+        k_dense_bwd) when the shape is one it serves and the minibatch has at least ``tuning.dense_bwd_min_rows`` rows; on the calling
+        stream even with overlap_wgrad, because dX is on the critical path.  Otherwise the pair ``wgrad`` then ``lin``; ``lin_W`` /
+        ``lin_K``: the weight image and contraction width of that GEMM where they are not W_nat / NOUT (a zero-padded copy)."""
+        if self._dense_bwd_fused(R, KIN, NOUT, act):
+            # with overlap_wgrad the side stream's weight gradients may still be folding their slabs out of wg_ws while this launch runs on
+            # the calling stream: it then gets a slab workspace of its own (sized for the largest shape served, allocated on first use)
+            ws = self.wg_ws if self._wgrad_side() is None else self.b.get("dense_ws", (self.L.call("magpo_wgrad_workspace_floats", 128, 64, self.G),))
+            self.L.call("magpo_dense_bwd", X, ldx, dY, ldy, W_nat, mask, lddx if mask is not None else 0, dX, lddx, R, KIN, NOUT, dW, db,
+                        ws, self._groups(R), act, self._st())
+            return
+        self.wgrad(X, ldx, dY, ldy, R, KIN, NOUT, dW, db)
+        self.lin(dY, ldy, W_nat if lin_W is None else lin_W, None, dX, lddx, R, lin_K or NOUT, KIN, act=act, mask=mask)
+
     def _join_wgrad(self):
         """End of a backward: the calling stream waits for the weight gradients queued on the side stream."""
         if self.overlap_wgrad and self.wgrad_stream is not None:

@@ -762,15 +762,14 @@ class SableGuider(NetBase):
         grid = L.call("magpo_row_grid", R)
         slab = lambda n, w=E: b.get("s_" + n, (grid, w))
         # ---- logit head
-        self.wgrad(t("hn"), E, dlogits, LW, R, E, K, gv["dec.head.dense1.kernel"], gv["dec.head.dense1.bias"])
         dhn = g("dhn")
-        self.lin(dlogits, LW, self.wt["h1_nat_pad"], None, dhn, E, R, LW, E)
+        self.dense_bwd(t("hn"), E, dlogits, LW, v["dec.head.dense1.kernel"], dhn, E, R, E, K, gv["dec.head.dense1.kernel"], gv["dec.head.dense1.bias"],
+                       lin_W=self.wt["h1_nat_pad"], lin_K=LW)
         dhp = g("dhp_l")
         L.call("magpo_headmid_bwd", t("hp"), E, v["dec.head.norm.scale"], dhn, E, None, None, 0, dhp, E, slab("a"), None, None, R, E, st)
         self.reduce(slab("a"), gv["dec.head.norm.scale"])
-        self.wgrad(t(f"x{nb}"), E, dhp, E, R, E, E, gv["dec.head.dense0.kernel"], gv["dec.head.dense0.bias"])
         dout = g("dout")
-        self.lin(dhp, E, v["dec.head.dense0.kernel"], None, dout, E, R, E, E)
+        self.dense_bwd(t(f"x{nb}"), E, dhp, E, v["dec.head.dense0.kernel"], dout, E, R, E, E, gv["dec.head.dense0.kernel"], gv["dec.head.dense0.bias"])
         # ---- decoder blocks, last to first.  incoming gradient of block k's output x_{k+1}: (din0 [+ din1])
         din0, din1 = dout, None
         drep_q, drep_r = None, None      # running sums of d(obs_rep): cross-retention query path / residual path
@@ -783,10 +782,16 @@ class SableGuider(NetBase):
                           kvg2[:, 2 * E:], 3 * E, dsum2, dr2, dkvg2[:, 2 * E:], 3 * E, R, gv[d + "ln2.scale"], gv[d + "ln3.scale"])
             self._ret_bwd(t(f"q2{k}"), E, kvg2, 3 * E, kvg2[:, E:], 3 * E, dr2, dq2, E, dkvg2, 3 * E, dkvg2[:, E:], 3 * E, dones,
                           f"st_2{k}", nseq, T, 1)
-            self.wgrad(t("reppe"), E, dq2, E, R, E, E, gv[d + "retn2.w_q"])
-            self.wgrad(t(f"cpe{k}"), E, dkvg2, 3 * E, R, E, 3 * E, gv[d + "retn2.w_kvg"])
             dreppe = g(f"dreppe_{k}"); dcpe = g("dcpe")
-            self.lin(dq2, E, v[d + "retn2.w_q"], None, dreppe, E, R, E, E)
+            # (the same predicate NetBase.dense_bwd routes on, asked here as well because the pair's launches of the two projections
+            # interleave below the threshold -- the two places must stay in step)
+            if self._dense_bwd_fused(R, E, E):
+                self.dense_bwd(t("reppe"), E, dq2, E, v[d + "retn2.w_q"], dreppe, E, R, E, E, gv[d + "retn2.w_q"])
+                self.wgrad(t(f"cpe{k}"), E, dkvg2, 3 * E, R, E, 3 * E, gv[d + "retn2.w_kvg"])
+            else:   # both weight gradients first (the side stream's order), then both dX
+                self.wgrad(t("reppe"), E, dq2, E, R, E, E, gv[d + "retn2.w_q"])
+                self.wgrad(t(f"cpe{k}"), E, dkvg2, 3 * E, R, E, 3 * E, gv[d + "retn2.w_kvg"])
+                self.lin(dq2, E, v[d + "retn2.w_q"], None, dreppe, E, R, E, E)
             self.lin(dkvg2, 3 * E, v[d + "retn2.w_kvg"], None, dcpe, E, R, 3 * E, E)
             if drep_q is None:
                 drep_q, drep_r = dreppe, dsum2
@@ -821,9 +826,8 @@ class SableGuider(NetBase):
                slab("a"), slab("b"), slab("c", 1), R, E, st)
         self.reduce(slab("a"), gv["enc.head.norm.scale"]); self.reduce(slab("b"), gv["enc.head.dense1.kernel"])
         self.reduce(slab("c", 1), gv["enc.head.dense1.bias"], P=1, stride=1)
-        self.wgrad(t("rep"), E, dhv, E, R, E, E, gv["enc.head.dense0.kernel"], gv["enc.head.dense0.bias"])
         drep_v = g("dout")
-        self.lin(dhv, E, v["enc.head.dense0.kernel"], None, drep_v, E, R, E, E)
+        self.dense_bwd(t("rep"), E, dhv, E, v["enc.head.dense0.kernel"], drep_v, E, R, E, E, gv["enc.head.dense0.kernel"], gv["enc.head.dense0.bias"])
         # ---- encoder blocks, last to first; d(rep) = value head + cross-retention queries + decoder residuals
         e0, e1, e2 = drep_v, drep_q, drep_r
         first_ln = True

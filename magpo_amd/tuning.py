@@ -46,6 +46,9 @@ class Tuning:
     ppo_fused_step: bool = True   # critic.step_pair: magpo_gru_cell_step (True) or the composed step of each network (False)
     ff_fused_step: bool = True    # ff_nets.act_pair: magpo_mlp_act_step (True) or the composed dense chain of each network (False)
     ff_sable_fused_act: bool = False  # ff_sable acting step: SableGuider.act_team_fused / magpo_ff_sable_act (True) or the chain SableGuider.act (False)
+    dense_bwd_min_rows: int = 16384   # NetBase.dense_bwd: rows from which a narrow dense layer's dW and dX come from one magpo_dense_bwd launch (64 x 256:
+                                      # the size from which magpo_wgrad uses its whole-matrix kernels); below it the pair magpo_wgrad + magpo_linear.  No
+                                      # environment variable: tests set the field
 
     @classmethod
     def from_env(cls, env=None) -> "Tuning":
