@@ -50,6 +50,14 @@ int magpo_coordsum_step(int* step_count, int* target, int* record, uint32_t* key
                         int maxval, const int* actions, int act_stride, float* reward, float* discount,
                         unsigned char* done, float* obs, int* obs_step, float* m_ep_ret, int* m_ep_len,
                         unsigned char* m_term, int auto_reset, magpo_stream_t stream);
+/* magpo_coordsum_step plus extras["real_next_obs"] (wrappers/auto_reset_wrapper.py:52-83; read by rec_iql.py:254-256): the same kernel, which
+ * also writes real_obs [N][A][A + 1] (nullable), the observation of the stepped state BEFORE any auto-reset.  It equals obs on steps
+ * without an episode end; every other output and the state are bit-identical to magpo_coordsum_step's. */
+int magpo_coordsum_step_real_obs(int* step_count, int* target, int* record, uint32_t* key, uint32_t* metrics_key,
+                                 float* run_ret, int* run_len, float* ep_ret, int* ep_len, int N, int A, int K, int TLIM,
+                                 int maxval, const int* actions, int act_stride, float* reward, float* discount,
+                                 unsigned char* done, float* obs, int* obs_step, float* m_ep_ret, int* m_ep_len,
+                                 unsigned char* m_term, int auto_reset, float* real_obs, magpo_stream_t stream);
 
 /* ---- Level-Based Foraging env + wrappers (mava/wrappers/jumanji.py:171-220 LbfWrapper with the always-on team reward, AgentID, AutoReset,
  * RecordEpisodeMetrics; the env itself is jumanji LevelBasedForaging-v0 with RandomGenerator(grid_size, fov, num_agents, num_food,
@@ -67,6 +75,15 @@ int magpo_lbf_step(int* agent_pos, int* agent_level, int* food_pos, int* food_le
                    const int* actions, int act_stride, float* reward, float* discount, unsigned char* done, float* obs,
                    int* obs_step, unsigned char* mask, float* m_ep_ret, int* m_ep_len, unsigned char* m_term,
                    int auto_reset, magpo_stream_t stream);
+/* magpo_lbf_step plus extras["real_next_obs"]: the same kernel, which also writes real_obs [N][A][A + 3 (NF + A)] and real_mask [N][A][6],
+ * the observation and action mask of the stepped state BEFORE any auto-reset (equal to obs / mask on steps without an episode end).  Both
+ * NULL: exactly magpo_lbf_step; one of them NULL is rejected before the launch. */
+int magpo_lbf_step_real_obs(int* agent_pos, int* agent_level, int* food_pos, int* food_level, unsigned char* food_eaten,
+                            int* step_count, uint32_t* key, uint32_t* metrics_key, float* run_ret, int* run_len, float* ep_ret,
+                            int* ep_len, int N, int A, int NF, int G, int fov, int max_level, int force_coop, int time_limit,
+                            const int* actions, int act_stride, float* reward, float* discount, unsigned char* done, float* obs,
+                            int* obs_step, unsigned char* mask, float* m_ep_ret, int* m_ep_len, unsigned char* m_term,
+                            int auto_reset, float* real_obs, unsigned char* real_mask, magpo_stream_t stream);
 
 /* ---- Robot Warehouse env + wrappers (mava/wrappers/jumanji.py:137-168 RwareWrapper, AgentID, AutoReset, RecordEpisodeMetrics; the env
  * itself is jumanji RobotWarehouse-v0 with RandomGenerator(column_height, shelf_rows, shelf_columns, num_agents, sensor_range,
@@ -434,6 +451,57 @@ int magpo_ppo_loss_fwd_bwd(const float* logits, long ld, const unsigned char* ma
                            double* workspace, float* loss_out, long R, int K, float clip_eps, float ent_coef,
                            float vf_coef, magpo_stream_t stream);
 int magpo_copy_rows(const float* src, long lds_, float* dst, long ldd, long R, int W, magpo_stream_t stream);
+
+/* ---- Q-learning (csrc/qlearn.hip; mava/systems/q_learning/anakin/rec_iql.py:210-401, networks/distributions.py:94-138) ----
+ * Shared contracts: no hidden state, arguments validated before any launch, no atomics, equal inputs give equal bits, and whatever changes
+ * from env step to env step (key, env-step counter, ring cursor) is read from device memory so that a captured rollout replays.
+ * UNPINNED: tfp's Categorical(probs).sample, flashbax's trajectory buffer and optax's target updates are not in the reference tree; these
+ * entry points agree bit for bit with their restatement in tests/iql_ref.py.
+ *
+ * MaskedEpsGreedyDistribution(q, eps, mask).sample, one row per (env, agent): q [R][ld] with K <= 32 valid columns, mask [R][K] u8
+ * (nullable = all legal; a row needs one legal action), key = (k0, k1) or key_dev (device, overrides).  eps = max(eps_min, 1 - (t / eps_decay)
+ * * (1 - eps_min)) in fp32 in that order with t = t_dev[0]; t_dev NULL = eps 0.  probs = eps * mask / n_avail + (1 - eps) * onehot(greedy),
+ * greedy = argmax of q over the legal actions (first maximum); action = argmax_k(log(probs_k) + gumbel(counter r K + k)), the log rounded
+ * once from double like the gumbel.  With eps = 0 action = greedy whatever the key.  action [R] i32; greedy [R] i32 nullable.
+ * Rejected: K < 1, K > 32, ld < K, R K >= 2^32, NULL q / action, and (with t_dev) eps_decay <= 0 or eps_min outside [0, 1]. */
+int magpo_eps_greedy_sample(const float* q, long ld, const unsigned char* mask, uint32_t k0, uint32_t k1,
+                            const uint32_t* key_dev, const int* t_dev, float eps_min, float eps_decay, int* action,
+                            int* greedy, long R, int K, magpo_stream_t stream);
+/* Trajectory ring of one group: every field is a time ring [N][S] (S = buffer_size): r_obs / r_next_obs [N][S][A][F] dense rows,
+ * r_mask / r_next_mask [N][S][A][K] u8 (both NULL for envs without masks), r_action i32 / r_reward f32 [N][S][A], r_terminal / r_tot
+ * (term_or_trunc) [N][S] u8.  magpo_replay_add copies one env step (obs rows with stride ldo, next_obs rows = real_next_obs with stride
+ * ldn, mask / next_mask [N][A][K], action / reward [N][A], terminal / tot [N]) into slot cursor[0] of every env, then a second one-thread
+ * launch sets cursor = (cursor + 1) % S and filled = min(filled + 1, S) (device ints, plain stores).  A cursor outside [0, S) is clamped. */
+int magpo_replay_add(float* r_obs, unsigned char* r_mask, int* r_action, float* r_reward, unsigned char* r_terminal,
+                     unsigned char* r_tot, float* r_next_obs, unsigned char* r_next_mask, int* cursor, int* filled, int N,
+                     int S, int A, int F, int K, const float* obs, long ldo, const unsigned char* mask, const int* action,
+                     const float* reward, const unsigned char* terminal, const unsigned char* tot, const float* next_obs,
+                     long ldn, const unsigned char* next_mask, magpo_stream_t stream);
+/* The L - 1 aligned training rows of B sampled windows (rec_iql.py:335-350), window b = steps (start[b] + t) % S, t < L, of env env_idx[b]
+ * (device i32; env rows are clamped to [0, N), starts taken mod S), in the row order GruActor.seq_fwd reads: (b, t, agent), t < L - 1.
+ * o_obs (stride ldo) / o_tot [B][L-1] / o_action / o_reward from steps 0 .. L-2; o_next_obs (stride ldn) / o_next_mask [rows][K] from the same
+ * steps' real-next fields; o_next_tot / o_next_terminal [B][L-1] from steps 1 .. L-1.  Only the F leading floats of an output row are written.
+ * Rejected: B < 1, L < 2, L > S, NULL indices or outputs, strides < F. */
+int magpo_replay_gather(const float* r_obs, const unsigned char* r_mask, const int* r_action, const float* r_reward,
+                        const unsigned char* r_terminal, const unsigned char* r_tot, const float* r_next_obs,
+                        const unsigned char* r_next_mask, int N, int S, int A, int F, int K, const int* env_idx,
+                        const int* start, int B, int L, float* o_obs, long ldo, unsigned char* o_tot, int* o_action,
+                        float* o_reward, float* o_next_obs, long ldn, unsigned char* o_next_mask, unsigned char* o_next_tot,
+                        unsigned char* o_next_terminal, magpo_stream_t stream);
+/* Double-Q TD loss and its backward over R = B (L - 1) A rows (rec_iql.py:366-377, :299-328): next_a = argmax of q_online_next over the
+ * legal next actions (first maximum; next_mask [R][K] nullable), target = reward + (1 - next_terminal[r / A]) * gamma * q_target_next[next_a],
+ * q_sel = q_online[action].  dq [R][lddq] = 2 (q_sel - target) / R in column action and exactly 0 in every other column up to
+ * min(lddq, 64) (what seq_bwd expects of dlogits); loss_out [3] = [q_loss, mean_q, mean_target] by a two-stage reduction in a fixed order
+ * (bit-stable), workspace >= 8 * 1024 doubles.  All three Q inputs share the row stride ld.
+ * Rejected: R < 1 or not a multiple of A, K > 32, K > ld, K > lddq, lddq not a multiple of 4, any NULL pointer but next_mask. */
+int magpo_q_td_loss(const float* q_online, const float* q_online_next, const float* q_target_next, long ld, const int* action,
+                    const unsigned char* next_mask, const float* reward, const unsigned char* next_terminal, float gamma,
+                    float* dq, long lddq, double* workspace, float* loss_out, long R, int K, int A, magpo_stream_t stream);
+/* Target network over the flat parameter vectors.  mode 0: target = tau * online + (1 - tau) * target (optax.incremental_update), two fp32
+ * products and one sum, never contracted.  mode 1: target = online when t_train[0] % update_period == 0, else unchanged
+ * (optax.periodic_update; t_train a device int, its value before the increment, rec_iql.py:389-396). */
+int magpo_target_update(const float* online, float* target, long n, int mode, float tau, const int* t_train,
+                        int update_period, magpo_stream_t stream);
 
 /* ---- K10 optimiser: optax clip_by_global_norm + adam(eps=1e-5) (rec_magpo.py:581-589, :412-420) ---- */
 int magpo_clip_adam(float* params, const float* grads, float* mu, float* nu, long n, float grad_scale,

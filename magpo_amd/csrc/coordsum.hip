@@ -51,14 +51,17 @@ __device__ __forceinline__ int core_reset(const CoordSumState& s, const CoordSum
   return __shfl(first, 0, 64);
 }
 
-__device__ __forceinline__ void write_obs(float* __restrict__ obs, int* __restrict__ obs_step, long n, const CoordSumCfg& c,
-                                          int target_val, int step, int lane) {
+__device__ __forceinline__ void write_obs_rows(float* __restrict__ obs, long n, const CoordSumCfg& c, int target_val, int lane) {
   const int F = c.A + 1;
   float* o = obs + n * (long)c.A * F;
   for (int i = lane; i < c.A * F; i += 64) {
     int a = i / F, f = i - a * F;
     o[i] = f < c.A ? (f == a ? 1.f : 0.f) : (float)target_val;
   }
+}
+__device__ __forceinline__ void write_obs(float* __restrict__ obs, int* __restrict__ obs_step, long n, const CoordSumCfg& c,
+                                          int target_val, int step, int lane) {
+  write_obs_rows(obs, n, c, target_val, lane);
   if (lane == 0) obs_step[n] = step;
 }
 
@@ -111,6 +114,7 @@ __global__ __launch_bounds__(256) void k_coordsum_step(CoordSumState s, CoordSum
   int obs_target = tgt[min(steps, c.TLIM)];
   int obs_step = steps;
   if (lane == 0) s.step_count[n] = steps;
+  if (o.real_obs) write_obs_rows(o.real_obs, n, c, obs_target, lane);   // extras["real_next_obs"]: the stepped state's observation
   if (done && auto_reset) {
     uint32_t k0 = s.key[2 * n], k1 = s.key[2 * n + 1], nk0, nk1;
     split_key_first(k0, k1, nk0, nk1);
@@ -157,6 +161,21 @@ extern "C" int magpo_coordsum_step(int* step_count, int* target, int* record, ui
   StepOut o{reward, discount, done, obs, A + 1, obs_step, nullptr, m_ep_ret, m_ep_len, m_term};   // dense rows
   hipLaunchKernelGGL(k_coordsum_step, dim3((N + 3) / 4), dim3(256), 0, st, s, c, actions, act_stride, o, auto_reset);
   return check_launch("magpo_coordsum_step");
+}
+
+// magpo_coordsum_step + extras["real_next_obs"]: the same kernel with StepOut::real_obs set
+extern "C" int magpo_coordsum_step_real_obs(int* step_count, int* target, int* record, uint32_t* key, uint32_t* metrics_key,
+                                            float* run_ret, int* run_len, float* ep_ret, int* ep_len, int N, int A, int K, int TLIM,
+                                            int maxval, const int* actions, int act_stride, float* reward, float* discount,
+                                            unsigned char* done, float* obs, int* obs_step, float* m_ep_ret, int* m_ep_len,
+                                            unsigned char* m_term, int auto_reset, float* real_obs, hipStream_t st) {
+  if (int e = check_cfg(N, A, K, TLIM)) return e;
+  if (int e = env_args(N); e != ENV_LAUNCH) return e;
+  CoordSumState s{step_count, target, record, key, {metrics_key, run_ret, run_len, ep_ret, ep_len}};
+  CoordSumCfg c{N, A, K, TLIM, maxval};
+  StepOut o{reward, discount, done, obs, A + 1, obs_step, nullptr, m_ep_ret, m_ep_len, m_term, real_obs, nullptr};
+  hipLaunchKernelGGL(k_coordsum_step, dim3((N + 3) / 4), dim3(256), 0, st, s, c, actions, act_stride, o, auto_reset);
+  return check_launch("magpo_coordsum_step_real_obs");
 }
 
 // ---- input classes of the networks' first layers (csrc/classtab.hip) for wrapped CoordSum observations -----------------

@@ -42,6 +42,11 @@ struct StepOut {
   int* obs_step;          // [N]    observation.step_count
   unsigned char* mask;    // [N][A][K] action mask, NULL for envs without illegal actions
   float* m_ep_ret; int* m_ep_len; unsigned char* m_term;   // [N] extras["episode_metrics"]
+  // extras["real_next_obs"] (auto_reset_wrapper.py:52-83), both NULL unless a <env>_step_real_obs entry point passes them: the observation
+  // and action mask of the stepped state BEFORE any auto-reset, in the layout of obs (row stride ldo) / mask; equal to them on steps
+  // without an episode end.  Written by the CoordSum and LBF kernels only.
+  float* real_obs = nullptr;
+  unsigned char* real_mask = nullptr;
 };
 
 // RecordEpisodeMetrics.step (episode_metrics.py:79-112); mean_reward = the mean over agents of the step's rewards, formed by the caller

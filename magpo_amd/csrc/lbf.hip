@@ -232,6 +232,9 @@ __global__ __launch_bounds__(64) void k_lbf_step(LbfState s, LbfCfg c, const int
   const int steps = s.step_count[n] + 1;
   const bool done = all || steps >= c.TLIM;
   int obs_step = steps;
+  const int F = A + 3 * (NF + A);
+  // extras["real_next_obs"]: the stepped state's observation and mask, before an auto-reset replaces the state
+  if (o.real_obs) lbf_observe(c, e, o.real_obs + n * (long)A * F, o.real_mask + n * (long)A * LBF_NACT);
   if (done && auto_reset) {
     uint32_t k0 = s.key[2 * n], k1 = s.key[2 * n + 1], nk0, nk1, sk0, sk1;
     split_key_first(k0, k1, nk0, nk1);
@@ -241,7 +244,6 @@ __global__ __launch_bounds__(64) void k_lbf_step(LbfState s, LbfCfg c, const int
   }
   lbf_store(s, c, n, e);
   s.step_count[n] = obs_step;
-  const int F = A + 3 * (NF + A);
   lbf_observe(c, e, o.obs + n * (long)A * F, o.mask + n * (long)A * LBF_NACT);
   o.obs_step[n] = obs_step;
   write_team_outputs(o, n, A, team, all, done);   // termination = all food eaten; the time limit truncates (discount 1)
@@ -289,4 +291,24 @@ extern "C" int magpo_lbf_step(int* agent_pos, int* agent_level, int* food_pos, i
   StepOut o{reward, discount, done, obs, A + 3 * (NF + A), obs_step, mask, m_ep_ret, m_ep_len, m_term};   // dense rows
   hipLaunchKernelGGL(k_lbf_step, env_grid(N), dim3(ENV_BLOCK), 0, st, s, c, actions, act_stride, o, auto_reset);
   return check_launch("magpo_lbf_step");
+}
+
+// magpo_lbf_step + extras["real_next_obs"]: the same kernel with StepOut::real_obs / real_mask set (both or neither)
+extern "C" int magpo_lbf_step_real_obs(int* agent_pos, int* agent_level, int* food_pos, int* food_level, unsigned char* food_eaten,
+                                       int* step_count, uint32_t* key, uint32_t* metrics_key, float* run_ret, int* run_len, float* ep_ret,
+                                       int* ep_len, int N, int A, int NF, int G, int fov, int max_level, int force_coop, int time_limit,
+                                       const int* actions, int act_stride, float* reward, float* discount, unsigned char* done, float* obs,
+                                       int* obs_step, unsigned char* mask, float* m_ep_ret, int* m_ep_len, unsigned char* m_term,
+                                       int auto_reset, float* real_obs, unsigned char* real_mask, hipStream_t st) {
+  LbfState s{agent_pos, agent_level, food_pos, food_level, food_eaten, step_count, key, {metrics_key, run_ret, run_len, ep_ret, ep_len}};
+  LbfCfg c{N, A, NF, G, fov, max_level, force_coop, time_limit};
+  if (int e = lbf_check(c)) return e;
+  if ((real_obs == nullptr) != (real_mask == nullptr)) {
+    set_error("lbf_step_real_obs: real_obs and real_mask must both be given or both be NULL");
+    return MAGPO_EINVAL;
+  }
+  if (int e = env_args(N); e != ENV_LAUNCH) return e;
+  StepOut o{reward, discount, done, obs, A + 3 * (NF + A), obs_step, mask, m_ep_ret, m_ep_len, m_term, real_obs, real_mask};
+  hipLaunchKernelGGL(k_lbf_step, env_grid(N), dim3(ENV_BLOCK), 0, st, s, c, actions, act_stride, o, auto_reset);
+  return check_launch("magpo_lbf_step_real_obs");
 }

@@ -153,6 +153,7 @@ class EnvBatch:
     prefix = ""
     state_fields: Tuple[str, ...] = ()
     takes_ldo = takes_mask = False
+    has_real_obs = False   # the env has a <prefix>_step_real_obs entry point
     WRAPPER_TENSORS: TensorSpecs = dict(key=(I32, (2,)), metrics_key=(I32, (2,)), run_ret=(F32, ()), run_len=(I32, ()), ep_ret=(F32, ()),
                                         ep_len=(I32, ()))
 
@@ -178,14 +179,22 @@ class EnvBatch:
         self.L.call(self.prefix + "_reset", *self._args(), env_keys, *self._obs_args(obs, obs_step, mask),
                     torch.cuda.current_stream().cuda_stream)
 
-    def step(self, actions, reward, done, obs, obs_step, m_ret, m_len, m_term, auto_reset=True, mask=None, discount=None):
-        self.L.call(self.prefix + "_step", *self._args(), actions, self.cfg.num_agents, reward, discount, done,
-                    *self._obs_args(obs, obs_step, mask), m_ret, m_len, m_term, 1 if auto_reset else 0, torch.cuda.current_stream().cuda_stream)
+    def step(self, actions, reward, done, obs, obs_step, m_ret, m_len, m_term, auto_reset=True, mask=None, discount=None, real_obs=None,
+             real_mask=None):
+        """``real_obs`` / ``real_mask``: extras["real_next_obs"] (auto_reset_wrapper.py:52-83), the stepped state's observation and mask before
+        any auto-reset, through the env's ``_step_real_obs`` entry point (CoordSum and LBF have one)."""
+        name, real = self.prefix + "_step", ()
+        if real_obs is not None or real_mask is not None:
+            if not self.has_real_obs:
+                raise NotImplementedError(f"{type(self.cfg).__name__}: the env kernel does not write real_next_obs (CoordSum and LBF do)")
+            name, real = name + "_real_obs", (real_obs, *((real_mask,) if self.takes_mask else ()))
+        self.L.call(name, *self._args(), actions, self.cfg.num_agents, reward, discount, done,
+                    *self._obs_args(obs, obs_step, mask), m_ret, m_len, m_term, 1 if auto_reset else 0, *real, torch.cuda.current_stream().cuda_stream)
 
 
 class CoordSumEnvBatch(EnvBatch):
     """Wrapped CoordSum envs (csrc/coordsum.hip; state surface of coordsum/env.py:17-26)."""
-    prefix = "magpo_coordsum"
+    prefix, has_real_obs = "magpo_coordsum", True
     state_fields = ("step_count", "target", "record", "key", "metrics_key", "run_ret", "run_len", "ep_ret", "ep_len")
 
     def tensors(self):
@@ -199,7 +208,7 @@ class CoordSumEnvBatch(EnvBatch):
 
 class LbfEnvBatch(EnvBatch):
     """Wrapped Level-Based Foraging envs (csrc/lbf.hip; UNPINNED dynamics, see oracle/lbf.py)."""
-    prefix, takes_mask = "magpo_lbf", True
+    prefix, takes_mask, has_real_obs = "magpo_lbf", True, True
     state_fields = ("agent_pos", "agent_level", "food_pos", "food_level", "food_eaten", "step_count", "key", "metrics_key",
                     "run_ret", "run_len", "ep_ret", "ep_len")
 

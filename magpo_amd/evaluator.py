@@ -106,6 +106,39 @@ def make_ff_eval_act_fn(actor_apply_fn, config) -> Callable:
     return eval_act_fn
 
 
+def make_q_eval_act_fn(q_apply_fn, config) -> Callable:
+    """Makes ``EvalActFn(params, timestep, key, actor_state) -> (action, actor_state)`` for a recurrent Q network (rec_iql.py:516-529):
+    ``q_apply_fn`` is the ``GruQNetwork`` that owns the kernels.  The eps-greedy distribution is built with its default eps = 0, so the sample is
+    the masked greedy action whatever ``key`` is (magpo_eps_greedy_sample with a null step counter); the GRU state is carried in
+    ``actor_state["hidden_state"]`` [N * A, 128]."""
+    net = q_apply_fn
+    L = lib()
+    loaded = {"params": None}
+
+    def eval_act_fn(params: Dict[str, torch.Tensor], timestep, key: np.ndarray, actor_state):
+        if params is not None and params is not net.named and params is not loaded["params"]:
+            net.load_named(params)
+            loaded["params"] = params
+        view, mask = timestep.observation.agents_view, timestep.observation.action_mask
+        N, A = view.shape[0], view.shape[1]
+        if view.stride(2) != 1 or view.stride(1) != net.Fld or view.stride(0) != A * net.Fld:
+            raise ValueError(f"agents_view rows must be {net.Fld} floats apart (got strides {tuple(view.stride())})")
+        if mask is not None:
+            mask = mask.to(torch.uint8).contiguous()
+        h_in = actor_state["hidden_state"]
+        h_out = actor_state.get("_spare")
+        if h_out is None or h_out.shape != h_in.shape or h_out.data_ptr() == h_in.data_ptr():
+            h_out = torch.empty_like(h_in)
+        q = net.step(view, h_in, timestep.last().to(torch.uint8), h_out)
+        action = torch.empty(N, A, dtype=torch.int32, device=view.device)
+        key = np.asarray(key, dtype=np.uint32).reshape(2)
+        L.call("magpo_eps_greedy_sample", q, 64, mask, int(key[0]), int(key[1]), None, None, 0.0, 1.0, action, None, N * A, net.K,
+               torch.cuda.current_stream().cuda_stream)
+        return action, {"hidden_state": h_out, "_spare": h_in}
+
+    return eval_act_fn
+
+
 def get_eval_fn(env, act_fn: Callable, config, absolute_metric: bool, device=None, n_devices: int = 1):
     """``EvalFn(params, key, init_act_state) -> metrics`` (evaluator.py:66-185) over the MarlEnv contract: ``env.reset(keys)``,
     then ``time_limit + 1`` times ``act_fn(params, timestep, act_key, actor_state)`` and ``env.step(env_state, action)``; the

@@ -178,11 +178,12 @@ def train_and_evaluate_ff_actor(config, env, eval_env, learn, actor_network, lea
                               init_act_state=lambda batch: {}, eval_params=lambda state: state.params.actor_params)
 
 
-def train_and_evaluate(config, env, eval_env, learn, learner_state, eval_act_fn, key, key_e, device, rank, world, *, init_act_state, eval_params) -> float:
+def train_and_evaluate(config, env, eval_env, learn, learner_state, eval_act_fn, key, key_e, device, rank, world, *, init_act_state, eval_params,
+                       misc_metrics=None) -> float:
     """The experiment loop both systems run after their set-up (rec_magpo.py:702-815, rec_sable.py:518-620): evaluator, timestep
     bookkeeping, logger, checkpoint save / resume, ``num_evaluation`` x (learn, evaluate the pre-interval parameters), absolute metric.
     ``init_act_state(batch)``: the evaluator's initial actor state for ``batch`` envs; ``eval_params(learner_state)``: the parameter
-    dict the act function evaluates."""
+    dict the act function evaluates; ``misc_metrics(t)``: what a system logs under MISC next to the timestep (rec_iql's epsilon)."""
     n_devices = world
     evaluator = get_eval_fn(eval_env, eval_act_fn, config, absolute_metric=False, device=device, n_devices=n_devices)
 
@@ -234,7 +235,7 @@ def train_and_evaluate(config, env, eval_env, learn, learner_state, eval_act_fn,
         term = em["is_terminal_step"]
         ep_completed = bool(term.any())
         if logger:
-            logger.log({"timestep": t}, t, eval_step, LogEvent.MISC)
+            logger.log({"timestep": t, **(misc_metrics(t) if misc_metrics is not None else {})}, t, eval_step, LogEvent.MISC)
             if ep_completed:
                 logger.log({"episode_return": em["episode_return"][term], "episode_length": em["episode_length"][term],
                             "steps_per_second": steps_per_rollout / elapsed}, t, eval_step, LogEvent.ACT)

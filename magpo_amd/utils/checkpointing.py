@@ -52,7 +52,8 @@ def _rank_path(path: str, rank: int) -> str:
 
 
 # what differs between ranks (params / opt_states are replicated); the Sable system's state has no "dones" (its timestep carries last())
-ROLLOUT_FIELDS = ("key", "env_state", "timestep", "dones", "hstates")
+ROLLOUT_FIELDS = ("key", "env_state", "timestep", "dones", "hstates",
+                  "obs", "terminal", "term_or_trunc", "hidden_state", "time_steps", "buffer_state")   # (the second line: the Q-learning state)
 
 
 class Checkpointer:
@@ -217,6 +218,11 @@ def restore_learner_state(path: str, device="cuda", rank: int = 0, world: int = 
             return {k: dev(v) for k, v in x.items()}
         return x
 
+    if "buffer_state" in st:   # the Q-learning systems (systems/q_learning/types.py: LearnerState)
+        from ..systems.q_learning import types as ql
+        return ql.LearnerState(dev(st["obs"]), dev(st["terminal"]), dev(st["term_or_trunc"]), dev(st["hidden_state"]), dev(st["env_state"]),
+                               dev(st["time_steps"]), dev(st["train_steps"]), dev(st["opt_state"]), dev(st["buffer_state"]),
+                               ql.QNetParams(dev(st["params"]["online"]), dev(st["params"]["target"])), st["key"]), int(ck["timestep"])
     if "hstates" not in st and "dones" not in st:   # the memoryless Sable system (systems/sable/types.py: FFLearnerState)
         from ..systems.sable.types import FFLearnerState
         return FFLearnerState(dev(st["params"]), dev(st["opt_states"]), st["key"], dev(st["env_state"]), dev(st["timestep"])), int(ck["timestep"])
