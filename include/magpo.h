@@ -503,6 +503,61 @@ int magpo_q_td_loss(const float* q_online, const float* q_online_next, const flo
 int magpo_target_update(const float* online, float* target, long n, int mode, float tau, const int* t_train,
                         int update_period, magpo_stream_t stream);
 
+/* All L stored steps of B sampled windows (rec_qmix.py:377-395 unrolls over data_full.obs and never reads next_obs), indices as in
+ * magpo_replay_gather (clamped env rows, starts mod S): o_obs (stride ldo) / o_mask [rows][K] in row order (b, t, agent), t < L;
+ * o_tot [B][L]; o_action [B][L-1][A] from steps 0 .. L-2; o_reward [B][L-1] = agent column 0 of the reward ring of those steps (the team
+ * reward, which magpo_team_reward put into every column).  Rejected: B < 1, L < 2, L > S, NULL indices or outputs, ldo < F. */
+int magpo_replay_gather_seq(const float* r_obs, const unsigned char* r_mask, const int* r_action, const float* r_reward,
+                            const unsigned char* r_terminal, const unsigned char* r_tot, const float* r_next_obs,
+                            const unsigned char* r_next_mask, int N, int S, int A, int F, int K, const int* env_idx,
+                            const int* start, int B, int L, float* o_obs, long ldo, unsigned char* o_mask, unsigned char* o_tot,
+                            int* o_action, float* o_reward, magpo_stream_t stream);
+/* jnp.mean(reward, axis=-1) of one env step (rec_qmix.py:287): out [N][A], every agent column = (((r_0 + r_1) + ...) + r_{A-1}) / (float)A in
+ * fp32 in that order.  out may be reward itself. */
+int magpo_team_reward(const float* reward, float* out, int N, int A, magpo_stream_t stream);
+
+/* ---- QMIX mixing network (csrc/qmix.hip; QMixingNetwork, mava/networks/base.py:276-343; rec_qmix.py:344-425) ----
+ * For a row with agent values q[A] and global state s[G]: x = LayerNorm(s) * scale + bias (rstd = rsqrt(max(E[s^2] - E[s]^2, 0) + 1e-6); x = s
+ * without norm_env_states); w1 = |Dense(A E)(relu(Dense(64)(x)))|, b1 = Dense(E)(x), hidden = elu(q . w1 + b1); w2 = |Dense(E)(relu(Dense(64)(x)))|,
+ * b2 = Dense(1)(relu(Dense(E)(x))); q_tot = hidden . w2 + b2.
+ *   dims_host[11] = {A, E, G, F_raw, id_cols, norm_env_states, Tm, Ts, t_off, q mode, K}: E in {32, 64}, 1 <= A, A E <= 512, 1 <= G = A F_raw <= 128.
+ *   params + offs_host[16]: ONE parameter buffer and the offsets (floats, multiples of 4) of its entries, Dense kernels [in][out]:
+ *     hyper_w1 Dense_0 kernel [G][64], bias | hyper_w1 Dense_1 kernel [64][A E], bias | hyper_b1 Dense_0 kernel [G][E], bias |
+ *     hyper_w2 Dense_0 kernel [G][64], bias | hyper_w2 Dense_1 kernel [64][E], bias | hyper_b2 Dense_0 kernel [G][E], bias |
+ *     hyper_b2 Dense_1 kernel [E][1], bias [1] | layer_norm scale [G], bias [G].
+ *   Mixer row r is step r % Tm of sequence r / Tm; it reads team (r / Tm) Ts + r % Tm + t_off of the observation rows (Tm = Ts, t_off = 0: row
+ *   r reads team r).  The state is never materialised: s = the concatenation over the team's agents j of obs[team A + j][id_cols .. id_cols +
+ *   F_raw) (row stride ldo), the layout of magpo_global_state.
+ *   q mode 0: q [R][A].  Mode 1: q = Q rows [teams A][ldq], K valid columns, and agent a of row r takes column index[r A + a] (clamped to
+ *   [0, K)) of row team A + a.  Mode 2 (double-Q selection): the column is the first maximum of q_online's row over the legal actions
+ *   (mask [teams A][K] u8, nullable), taken from q's row.  q_used [R][A] (nullable without save) receives the values that were mixed.
+ * magpo_qmix_fwd: q_tot [R] in ONE launch.  save (nullable) = the training mode: [R][magpo_qmix_save_floats(E, G)] floats per row, the two
+ *   64-wide hypernetwork hiddens | hyper_b2's hidden [E] | hidden [E] | xhat [round4(G)] (s itself without normalisation) | rstd.
+ * magpo_qmix_bwd: from dq_tot [R], one launch + magpo_reduce_slabs: dq [R][A] (nullable) and grads [P] = the gradient of every entry at the
+ *   offsets of params (padding between entries zero; the layer_norm entries zero without normalisation).  slab: workspace of
+ *   magpo_qmix_bwd_grid(R) * P floats, 16-byte aligned; per-workgroup partial sums folded in a fixed order: no atomics, equal inputs give equal
+ *   bits.  d|x|/dx = sign(x) with sign(0) = 0; elu' = 1 for x > 0, else exp(x).  dq64 (nullable; needs index, lddq = 64, K): the scatter for
+ *   seq_bwd: row team A + a of dq64 takes dq[r][a] in column index[r A + a] and zero in its other 63 columns; rows of teams that no mixer row
+ *   reads are not written.  dims / offsets as the forward's (the q mode is not read).
+ * Rejected before a pointer is touched: a shape outside the limits above, R < 1, table sizes other than 11 / 16, an offset that is negative,
+ *   not a multiple of 4 or (bwd) outside P, strides that do not cover their rows, a NULL pointer in a required slot. */
+long magpo_qmix_save_floats(int E, int G);
+long magpo_qmix_bwd_grid(long R);
+int magpo_qmix_fwd(const int* dims_host, int ndims, const float* params, const long* offs_host, int noffs, const float* obs, long ldo,
+                   const float* q, const float* q_online, long ldq, const int* index, const unsigned char* mask, float* q_tot,
+                   float* q_used, float* save, long R, magpo_stream_t stream);
+int magpo_qmix_bwd(const int* dims_host, int ndims, const float* params, const long* offs_host, int noffs, long P, const float* save,
+                   const float* q_used, const float* dq_tot, float* dq, float* dq64, long lddq, const int* index, float* slab,
+                   float* grads, long R, magpo_stream_t stream);
+/* TD target and loss of rec_qmix (rec_qmix.py:358-367, :413, :423-425) over R = U B (L - 1) rows (b, t) of U stacked groups: next_done =
+ * term_or_trunc [U B][L] at step t + 1 (NOT terminal: QMIX cuts the bootstrap at truncation too); target = reward + (1 - next_done) * gamma *
+ * next_q_tot, every operation rounded to fp32 in that order; dq_tot = 2 / R * (q_tot - target); loss_out [8] = [q_loss, mean_q, max_q_error,
+ * min_q_error, mean_target, mean_reward_t0, mean_next_qval, done]: sums in double in a fixed order, max / min of err^2 per group averaged over the
+ * groups (the reference's pmean), done = mean of term_or_trunc over all L steps.  workspace >= 8 U doubles.
+ * Rejected: L < 2, U outside 1..1024, R < 1 or not a multiple of U (L - 1), a NULL pointer. */
+int magpo_qmix_td_loss(const float* q_tot, const float* next_q_tot, const float* reward, const unsigned char* term_or_trunc, int L,
+                       float gamma, float* dq_tot, double* workspace, float* loss_out, long R, int U, magpo_stream_t stream);
+
 /* ---- K10 optimiser: optax clip_by_global_norm + adam(eps=1e-5) (rec_magpo.py:581-589, :412-420) ---- */
 int magpo_clip_adam(float* params, const float* grads, float* mu, float* nu, long n, float grad_scale,
                     float max_norm, float lr, float b1, float b2, float eps, float bc1, float bc2,

@@ -10,21 +10,9 @@
 #include <cstdio>
 
 #include "common.hpp"
+#include "qselect.hpp"
 
 namespace magpo {
-
-constexpr float Q_FMIN = -3.4028234663852886e38f;  // jnp.finfo(float32).min: what an illegal action's Q value is replaced by
-
-// argmax over the legal columns of one Q row, first maximum wins (jnp.argmax of where(mask, q, finfo.min)); m == nullptr: all legal
-__device__ __forceinline__ int masked_argmax(const float* __restrict__ q, const unsigned char* __restrict__ m, int K) {
-  float best = (m && !m[0]) ? Q_FMIN : q[0];
-  int arg = 0;
-  for (int k = 1; k < K; ++k) {
-    const float v = (m && !m[k]) ? Q_FMIN : q[k];
-    if (v > best) { best = v; arg = k; }
-  }
-  return arg;
-}
 
 // ---- eps-greedy sampling: one thread per (env, agent) row -------------------------------------------------------------------------
 struct EpsGreedyArgs {
@@ -146,6 +134,49 @@ __global__ void k_replay_gather(Ring g, const int* __restrict__ env_idx, const i
     o.next_tot[i] = g.tot[s1];
     o.next_terminal[i] = g.terminal[s1];
   }
+}
+
+// all L stored steps of every window (rec_qmix.py:377-395 unrolls over data_full.obs): flat over max(rows * F, rows * K, rows) like
+// k_replay_gather, rows = B L A
+struct GatherSeqOut {
+  float* obs; long ldo; unsigned char* mask; unsigned char* tot; int* action; float* reward;
+};
+__global__ void k_replay_gather_seq(Ring g, const int* __restrict__ env_idx, const int* __restrict__ start, int B, int L, GatherSeqOut o) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int A = g.A, F = g.F, K = g.K, T = L - 1;
+  const long rows = (long)B * L * A;
+  auto slot_of = [&](int b, int t) -> long {   // ring slot of step t of window b
+    int n = env_idx[b], s0 = start[b];
+    n = n < 0 ? 0 : (n >= g.N ? g.N - 1 : n);     // indices come from device memory: clamp, never read outside the ring
+    s0 = ((s0 % g.S) + g.S) % g.S;
+    return (long)n * g.S + (s0 + t) % g.S;
+  };
+  if (i < rows * F) {
+    const long r = i / F, bt = r / A;
+    const int f = (int)(i - r * F), ag = (int)(r - bt * A);
+    o.obs[r * o.ldo + f] = g.obs[(slot_of((int)(bt / L), (int)(bt % L)) * A + ag) * F + f];
+  }
+  if (g.mask && i < rows * K) {
+    const long r = i / K, bt = r / A;
+    const int k = (int)(i - r * K), ag = (int)(r - bt * A);
+    o.mask[i] = g.mask[(slot_of((int)(bt / L), (int)(bt % L)) * A + ag) * K + k];
+  }
+  if (i < (long)B * L) o.tot[i] = g.tot[slot_of((int)(i / L), (int)(i % L))];
+  if (i < (long)B * T * A) {
+    const long bt = i / A;
+    o.action[i] = g.action[slot_of((int)(bt / T), (int)(bt % T)) * A + i % A];
+  }
+  if (i < (long)B * T) o.reward[i] = g.reward[slot_of((int)(i / T), (int)(i % T)) * A];   // (every agent column holds the team reward)
+}
+
+// jnp.mean(reward, axis=-1) of one env step (rec_qmix.py:287), stored in every agent column: sequential fp32 sum over the agents, then / A
+__global__ void k_team_reward(const float* __restrict__ reward, float* __restrict__ out, int N, int A) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  float s = 0.f;
+  for (int a = 0; a < A; ++a) s = __fadd_rn(s, reward[(long)n * A + a]);
+  s = __fdiv_rn(s, (float)A);
+  for (int a = 0; a < A; ++a) out[(long)n * A + a] = s;
 }
 
 // ---- double-Q TD loss (rec_iql.py:366-377, :299-328): 16 lanes per row, 4 gradient columns per lane ------------------------------------
@@ -282,6 +313,32 @@ extern "C" int magpo_replay_gather(const float* r_obs, const unsigned char* r_ma
   const long rows = (long)B * (L - 1) * A, n = rows * (F > K ? F : K);
   hipLaunchKernelGGL(k_replay_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g, env_idx, start, B, L, o);
   return check_launch("magpo_replay_gather");
+}
+
+extern "C" int magpo_replay_gather_seq(const float* r_obs, const unsigned char* r_mask, const int* r_action, const float* r_reward,
+                                       const unsigned char* r_terminal, const unsigned char* r_tot, const float* r_next_obs,
+                                       const unsigned char* r_next_mask, int N, int S, int A, int F, int K, const int* env_idx,
+                                       const int* start, int B, int L, float* o_obs, long ldo, unsigned char* o_mask,
+                                       unsigned char* o_tot, int* o_action, float* o_reward, hipStream_t st) {
+  Ring g{const_cast<float*>(r_obs), const_cast<unsigned char*>(r_mask), const_cast<int*>(r_action), const_cast<float*>(r_reward),
+         const_cast<unsigned char*>(r_terminal), const_cast<unsigned char*>(r_tot), const_cast<float*>(r_next_obs),
+         const_cast<unsigned char*>(r_next_mask), N, S, A, F, K};
+  if (int e = ring_check("replay_gather_seq", g)) return e;
+  if (B < 1 || L < 2 || L > S) { set_error("replay_gather_seq: need B >= 1 and 2 <= L <= buffer_size"); return MAGPO_EINVAL; }
+  if (!env_idx || !start || !o_obs || !o_tot || !o_action || !o_reward || ldo < F || (r_mask && !o_mask)) {
+    set_error("replay_gather_seq: indices and outputs must not be NULL (mask where the ring has one), and the row stride must be >= F");
+    return MAGPO_EINVAL;
+  }
+  GatherSeqOut o{o_obs, ldo, o_mask, o_tot, o_action, o_reward};
+  const long rows = (long)B * L * A, n = rows * (F > K ? F : K);
+  hipLaunchKernelGGL(k_replay_gather_seq, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g, env_idx, start, B, L, o);
+  return check_launch("magpo_replay_gather_seq");
+}
+
+extern "C" int magpo_team_reward(const float* reward, float* out, int N, int A, hipStream_t st) {
+  if (N < 1 || A < 1 || !reward || !out) { set_error("team_reward: need N, A >= 1, reward and out not NULL"); return MAGPO_EINVAL; }
+  hipLaunchKernelGGL(k_team_reward, dim3((unsigned)((N + 127) / 128)), dim3(128), 0, st, reward, out, N, A);
+  return check_launch("magpo_team_reward");
 }
 
 // workspace: >= 8 * 1024 doubles (as magpo_ppo_loss_fwd_bwd)

@@ -10,10 +10,12 @@ from ._lib import lib
 
 
 class ClipAdam:
-    def __init__(self, net, sys):
+    def __init__(self, net, sys, eps: float = 1e-5, max_norm=None):
         """``net``: SableGuider / GruActor (flat parameters ``net.P.flat``, flat gradients ``net.grads``); ``sys``: SystemConfig (actor_lr,
-        max_grad_norm, decay_learning_rates, lr_num_updates, ppo_epochs, num_minibatches)."""
+        max_grad_norm, decay_learning_rates, lr_num_updates, ppo_epochs, num_minibatches).  ``eps``: adam's epsilon; ``max_norm``: the clipping
+        norm instead of ``sys.max_grad_norm`` (``inf``: optax.adam alone, the kernel then never clips and the step is element-wise)."""
         self.net, self.sys = net, sys
+        self.eps, self.max_norm = float(eps), max_norm
         self.mu, self.nu = torch.zeros_like(net.P.flat), torch.zeros_like(net.P.flat)
         self.count = 0
         self.last_lr = float(sys.actor_lr)
@@ -34,8 +36,8 @@ class ClipAdam:
         bc1 = float(np.float32(1) - np.float32(0.9) ** np.float32(cnt))
         bc2 = float(np.float32(1) - np.float32(0.999) ** np.float32(cnt))
         lr = self.learning_rate()
-        self.L.call("magpo_clip_adam", net.P.flat, net.grads, self.mu, self.nu, net.P.numel, grad_scale, s.max_grad_norm, lr,
-                    0.9, 0.999, 1e-5, bc1, bc2, ws64, gnorm_out, torch.cuda.current_stream().cuda_stream)
+        self.L.call("magpo_clip_adam", net.P.flat, net.grads, self.mu, self.nu, net.P.numel, grad_scale,
+                    s.max_grad_norm if self.max_norm is None else float(self.max_norm), lr, 0.9, 0.999, self.eps, bc1, bc2, ws64, gnorm_out, torch.cuda.current_stream().cuda_stream)
         self.count = cnt
         self.last_lr = lr
         net.refresh()

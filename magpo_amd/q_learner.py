@@ -176,7 +176,7 @@ class QLearner(AnakinLearner):
         self.q_opt = optim if optim is not None else ClipAdam(q_net, sys)
         assert self.q_opt.net is q_net
         self.groups: List[QGroup] = [QGroup(env_cfg, num_envs, self.T, S, device) for _ in range(num_groups)]
-        log.info("rec_iql: replay ring of %d steps x %d envs per group: %.2f MiB", S, num_envs, self.groups[0].ring_bytes() / 2 ** 20)
+        log.info(self.SYSTEMS + ": replay ring of %d steps x %d envs per group: %.2f MiB", S, num_envs, self.groups[0].ring_bytes() / 2 ** 20)
         self.t_train = 0
         self.t_train_dev = torch.zeros(1, dtype=torch.int32, device=device)
         self._idx_host = None
@@ -239,12 +239,16 @@ class QLearner(AnakinLearner):
             g.env.step(tr["action"][t], tr["reward"][t], tr["done"][t + 1], tr["obs"][t + 1], tr["step_count"][t + 1], g.metrics["episode_return"][t],
                        g.metrics["episode_length"][t], g.metrics["is_terminal_step"][t], mask=None if mk is None else tr["mask"][t + 1],
                        discount=g.discount, real_obs=g.real_obs, real_mask=g.real_mask)
+            self._before_add(g, t)
             L.call("magpo_replay_add", *g.ring_fields(), g.cursor, g.filled, N, g.S, A, self.Fld, K, tr["obs"][t], self.Fld, mk, tr["action"][t],
                    tr["reward"][t], g.term[t], tr["done"][t], g.real_obs, self.Fld, g.real_mask, st)
             g.term[t + 1].copy_(g.discount[:, 0] == 0)     # next_terminal = 1 - discount (:264)
             g.t_dev.add_(N)                                # t + num_envs (:233)
         if cur != 0:  # keep the buffer roles identical from rollout to rollout (static graph arguments)
             g.h[0].copy_(g.h[1])
+
+    def _before_add(self, g: QGroup, t: int):
+        """What a derived system does to the env step in slot t before it is stored (rec_qmix: the team reward); nothing here."""
 
     def _carry_over(self):
         super()._carry_over()

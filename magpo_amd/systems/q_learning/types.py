@@ -22,6 +22,13 @@ class QNetParams(NamedTuple):
     target: Dict[str, torch.Tensor]
 
 
+class QMIXParams(NamedTuple):
+    online: Dict[str, torch.Tensor]
+    target: Dict[str, torch.Tensor]
+    mixer_online: Dict[str, torch.Tensor]
+    mixer_target: Dict[str, torch.Tensor]
+
+
 class ActionSelectionState(NamedTuple):
     online_params: Dict[str, torch.Tensor]
     hidden_state: torch.Tensor

@@ -220,9 +220,11 @@ def restore_learner_state(path: str, device="cuda", rank: int = 0, world: int = 
 
     if "buffer_state" in st:   # the Q-learning systems (systems/q_learning/types.py: LearnerState)
         from ..systems.q_learning import types as ql
+        p = dev(st["params"])
+        params = ql.QMIXParams(p["online"], p["target"], p["mixer_online"], p["mixer_target"]) if "mixer_online" in p else ql.QNetParams(p["online"], p["target"])
         return ql.LearnerState(dev(st["obs"]), dev(st["terminal"]), dev(st["term_or_trunc"]), dev(st["hidden_state"]), dev(st["env_state"]),
                                dev(st["time_steps"]), dev(st["train_steps"]), dev(st["opt_state"]), dev(st["buffer_state"]),
-                               ql.QNetParams(dev(st["params"]["online"]), dev(st["params"]["target"])), st["key"]), int(ck["timestep"])
+                               params, st["key"]), int(ck["timestep"])
     if "hstates" not in st and "dones" not in st:   # the memoryless Sable system (systems/sable/types.py: FFLearnerState)
         from ..systems.sable.types import FFLearnerState
         return FFLearnerState(dev(st["params"]), dev(st["opt_states"]), st["key"], dev(st["env_state"]), dev(st["timestep"])), int(ck["timestep"])
