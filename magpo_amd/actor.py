@@ -63,6 +63,16 @@ class GruActor(TorsoNet):
         self.wg_ws = torch.empty(max(self.L.call("magpo_wgrad_workspace_floats", k, n, self.G) for k, n in shapes), device=device)
         self.refresh()
 
+    def _twin_kw(self):
+        return dict(wgrad_groups=self.G, tuning=self.tuning, obs_ld=self.Fld, pre_torso=self.pre_spec, post_torso=self.post_spec)
+
+    def twin(self):
+        """A second network of the same class, shape, row stride and torsos on the same device, sharing this one's ``Tuning`` object, with
+        buffers of its own and uninitialised parameters (``load_named`` fills them): what an evaluator acts with, so that loading the
+        evaluated parameters does not touch the learner's.  (A network built without ``tuning`` holds ``Tuning.from_env()`` of the same
+        process environment, so sharing the object gives a system's evaluation network the values a fresh default would have.)"""
+        return type(self)(self.A, self.K, self.F, self.dev, **self._twin_kw())
+
     def bind_grads(self, grads: torch.Tensor) -> None:
         """Make ``grads`` (flat, P.numel floats, e.g. a slice of the learner's all-reduce message) the gradient buffer."""
         assert grads.numel() == self.P.numel

@@ -84,6 +84,9 @@ class GruCritic(GruActor):
                 self.v["head.kernel"].mul_(100.0)
             self.refresh()
 
+    def twin(self):
+        return type(self)(self.A, self.F, self.dev, centralised=self.centralised, **self._twin_kw())
+
     def _values(self, logits, R, name):
         val = self.b.get(name, (R,))
         self.L.call("magpo_copy_rows", logits, 64, val, 1, R, 1, self._st())

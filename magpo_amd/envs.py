@@ -132,6 +132,17 @@ def host_split(key: np.ndarray, num: int = 2) -> np.ndarray:
     return out
 
 
+def agent_sample_keys(key: np.ndarray, A: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The key chain inside get_actions (decode.py:141): key, sample_key = split(key), once per agent in agent order.
+    Returns (the carried key, the A sample keys [A, 2])."""
+    k = np.asarray(key, dtype=np.uint32).reshape(2)
+    keys = np.zeros((A, 2), np.uint32)
+    for i in range(A):
+        kk = host_split(k, 2)
+        k, keys[i] = kk[0], kk[1]
+    return k, keys
+
+
 def prng_key(seed: int) -> np.ndarray:
     return np.array([(int(seed) >> 32) & 0xFFFFFFFF, int(seed) & 0xFFFFFFFF], np.uint32)
 

@@ -9,14 +9,14 @@ from __future__ import annotations
 import math
 import time
 import warnings
-from typing import Callable, Dict
+from typing import Callable, Dict, Optional
 
 import numpy as np
 import torch
 
 from ._lib import lib
 from .actor import GruActor
-from .learner import host_split
+from .envs import agent_sample_keys, host_split
 
 
 def get_num_eval_envs(config, absolute_metric: bool, n_devices: int = 1) -> int:
@@ -25,6 +25,49 @@ def get_num_eval_envs(config, absolute_metric: bool, n_devices: int = 1) -> int:
     if episodes <= n_parallel:
         return math.ceil(episodes / n_devices)
     return config.arch.num_envs
+
+
+# ---------------------------------------------------------------------- what the act functions share
+def _load_params(net, loaded, params) -> None:
+    """Load ``params`` into ``net`` when a DIFFERENT dict object arrives than the last one loaded (``net.named`` itself never needs loading)."""
+    if params is not None and params is not net.named and params is not loaded["params"]:
+        net.load_named(params)
+        loaded["params"] = params
+
+
+def _view_and_mask(net, timestep):
+    """(agents_view [N, A, F] with its rows checked to be ``net.Fld`` floats apart, action mask as contiguous uint8 or None)."""
+    view, mask = timestep.observation.agents_view, timestep.observation.action_mask
+    if view.stride(2) != 1 or view.stride(1) != net.Fld or view.stride(0) != view.shape[1] * net.Fld:
+        raise ValueError(f"agents_view rows must be {net.Fld} floats apart (got strides {tuple(view.stride())})")
+    return view, None if mask is None else mask.to(torch.uint8).contiguous()
+
+
+def _swap_hidden(actor_state):
+    """(h_in, h_out) of a recurrent step: the carried ``hidden_state`` and the ``_spare`` tensor the step writes (a new one when the state
+    has none of that shape yet); the step's actor state is {"hidden_state": h_out, "_spare": h_in}."""
+    h_in = actor_state["hidden_state"]
+    h_out = actor_state.get("_spare")
+    if h_out is None or h_out.shape != h_in.shape or h_out.data_ptr() == h_in.data_ptr():
+        h_out = torch.empty_like(h_in)
+    return h_in, h_out
+
+
+def _mode_or_sample(L, logits, mask, key, greedy: bool, N: int, A: int, K: int) -> torch.Tensor:
+    """Actions [N, A] int32 from logit rows [N * A, 64]: ``pi.mode()`` of the masked categorical (heads.py:56-63: illegal logits -> finfo.min)
+    or one magpo_sample_categorical draw over the whole batch from ``key``."""
+    action = torch.empty(N, A, dtype=torch.int32, device=logits.device)
+    if greedy:
+        lg = logits[:, :K]
+        if mask is not None:
+            lg = torch.where(mask.view(N * A, K) != 0, lg, torch.full_like(lg, torch.finfo(torch.float32).min))
+        action.copy_(lg.argmax(-1).view(N, A))
+    else:
+        key = np.asarray(key, dtype=np.uint32).reshape(2)
+        logp = torch.empty(N * A, device=logits.device)
+        L.call("magpo_sample_categorical", logits, 64, mask, 0 if mask is None else K, int(key[0]), int(key[1]), None, action, 1,
+               logp, 1, None, 0, None, 0, N * A, K, torch.cuda.current_stream().cuda_stream)
+    return action
 
 
 def make_rec_eval_act_fn(actor_apply_fn: GruActor, config) -> Callable:
@@ -36,36 +79,14 @@ def make_rec_eval_act_fn(actor_apply_fn: GruActor, config) -> Callable:
     greedy = bool(config.arch.evaluation_greedy)
     L = lib()
     loaded = {"params": None}
-    _hidden_state = "hidden_state"
 
     def eval_act_fn(params: Dict[str, torch.Tensor], timestep, key: np.ndarray, actor_state):
-        if params is not None and params is not actor.named and params is not loaded["params"]:
-            actor.load_named(params)
-            loaded["params"] = params
-        view, mask = timestep.observation.agents_view, timestep.observation.action_mask
-        N, A = view.shape[0], view.shape[1]
-        if view.stride(2) != 1 or view.stride(1) != actor.Fld or view.stride(0) != A * actor.Fld:
-            raise ValueError(f"agents_view rows must be {actor.Fld} floats apart (got strides {tuple(view.stride())})")
-        if mask is not None:
-            mask = mask.to(torch.uint8).contiguous()
+        _load_params(actor, loaded, params)
+        view, mask = _view_and_mask(actor, timestep)
         last_done = timestep.last().to(torch.uint8)          # repeated over the agents inside the kernel (evaluator.py:200)
-        h_in = actor_state[_hidden_state]
-        h_out = actor_state.get("_spare")
-        if h_out is None or h_out.shape != h_in.shape or h_out.data_ptr() == h_in.data_ptr():
-            h_out = torch.empty_like(h_in)
+        h_in, h_out = _swap_hidden(actor_state)
         logits = actor.step(view, h_in, last_done, h_out, want_logits=True)
-        action = torch.empty(N, A, dtype=torch.int32, device=view.device)
-        if greedy:   # pi.mode() of the masked categorical (heads.py:56-63: illegal logits -> finfo.min)
-            lg = logits[:, :actor.K]
-            if mask is not None:
-                lg = torch.where(mask.view(N * A, actor.K) != 0, lg, torch.full_like(lg, torch.finfo(torch.float32).min))
-            action.copy_(lg.argmax(-1).view(N, A))
-        else:
-            key = np.asarray(key, dtype=np.uint32).reshape(2)
-            logp = torch.empty(N * A, device=view.device)
-            L.call("magpo_sample_categorical", logits, 64, mask, 0 if mask is None else actor.K, int(key[0]), int(key[1]), None, action, 1,
-                   logp, 1, None, 0, None, 0, N * A, actor.K, torch.cuda.current_stream().cuda_stream)
-        return action, {_hidden_state: h_out, "_spare": h_in}
+        return _mode_or_sample(L, logits, mask, key, greedy, view.shape[0], view.shape[1], actor.K), {"hidden_state": h_out, "_spare": h_in}
 
     return eval_act_fn
 
@@ -80,28 +101,9 @@ def make_ff_eval_act_fn(actor_apply_fn, config) -> Callable:
     loaded = {"params": None}
 
     def eval_act_fn(params: Dict[str, torch.Tensor], timestep, key: np.ndarray, actor_state):
-        if params is not None and params is not actor.named and params is not loaded["params"]:
-            actor.load_named(params)
-            loaded["params"] = params
-        view, mask = timestep.observation.agents_view, timestep.observation.action_mask
-        N, A = view.shape[0], view.shape[1]
-        if view.stride(2) != 1 or view.stride(1) != actor.Fld or view.stride(0) != A * actor.Fld:
-            raise ValueError(f"agents_view rows must be {actor.Fld} floats apart (got strides {tuple(view.stride())})")
-        if mask is not None:
-            mask = mask.to(torch.uint8).contiguous()
-        logits = actor.logits(view)
-        action = torch.empty(N, A, dtype=torch.int32, device=view.device)
-        if greedy:   # pi.mode() of the masked categorical (heads.py:56-63: illegal logits -> finfo.min)
-            lg = logits[:, :actor.K]
-            if mask is not None:
-                lg = torch.where(mask.view(N * A, actor.K) != 0, lg, torch.full_like(lg, torch.finfo(torch.float32).min))
-            action.copy_(lg.argmax(-1).view(N, A))
-        else:
-            key = np.asarray(key, dtype=np.uint32).reshape(2)
-            logp = torch.empty(N * A, device=view.device)
-            L.call("magpo_sample_categorical", logits, 64, mask, 0 if mask is None else actor.K, int(key[0]), int(key[1]), None, action, 1,
-                   logp, 1, None, 0, None, 0, N * A, actor.K, torch.cuda.current_stream().cuda_stream)
-        return action, {}
+        _load_params(actor, loaded, params)
+        view, mask = _view_and_mask(actor, timestep)
+        return _mode_or_sample(L, actor.logits(view), mask, key, greedy, view.shape[0], view.shape[1], actor.K), {}
 
     return eval_act_fn
 
@@ -116,25 +118,49 @@ def make_q_eval_act_fn(q_apply_fn, config) -> Callable:
     loaded = {"params": None}
 
     def eval_act_fn(params: Dict[str, torch.Tensor], timestep, key: np.ndarray, actor_state):
-        if params is not None and params is not net.named and params is not loaded["params"]:
-            net.load_named(params)
-            loaded["params"] = params
-        view, mask = timestep.observation.agents_view, timestep.observation.action_mask
+        _load_params(net, loaded, params)
+        view, mask = _view_and_mask(net, timestep)
         N, A = view.shape[0], view.shape[1]
-        if view.stride(2) != 1 or view.stride(1) != net.Fld or view.stride(0) != A * net.Fld:
-            raise ValueError(f"agents_view rows must be {net.Fld} floats apart (got strides {tuple(view.stride())})")
-        if mask is not None:
-            mask = mask.to(torch.uint8).contiguous()
-        h_in = actor_state["hidden_state"]
-        h_out = actor_state.get("_spare")
-        if h_out is None or h_out.shape != h_in.shape or h_out.data_ptr() == h_in.data_ptr():
-            h_out = torch.empty_like(h_in)
+        h_in, h_out = _swap_hidden(actor_state)
         q = net.step(view, h_in, timestep.last().to(torch.uint8), h_out)
         action = torch.empty(N, A, dtype=torch.int32, device=view.device)
         key = np.asarray(key, dtype=np.uint32).reshape(2)
         L.call("magpo_eps_greedy_sample", q, 64, mask, int(key[0]), int(key[1]), None, None, 0.0, 1.0, action, None, N * A, net.K,
                torch.cuda.current_stream().cuda_stream)
         return action, {"hidden_state": h_out, "_spare": h_in}
+
+    return eval_act_fn
+
+
+def sable_eval_act_fn(net, actor_apply_fn: Callable, stateful: bool) -> Callable:
+    """The body of the two act functions that execute a Sable network itself, rec_sable.make_rec_sable_act_fn (``stateful``) and
+    ff_sable.make_ff_sable_eval_act_fn (see their docstrings): ``net`` owns ``actor_apply_fn``; the kernel's inputs and outputs are
+    allocated once per batch size (the acting kernel caches its pointer tables), the action is sampled from the per-agent keys of ``key``.
+    ``stateful``: ``actor_state["hidden_state"]`` (the three retention states in one tensor) is advanced IN PLACE and handed back;
+    otherwise the actor state is ``{}`` in and out."""
+    loaded = {"params": None}
+    bufs: Dict[int, Dict[str, torch.Tensor]] = {}
+
+    def eval_act_fn(params: Optional[Dict[str, torch.Tensor]], timestep, key: np.ndarray, actor_state):
+        _load_params(net, loaded, params)
+        ob = timestep.observation
+        view, N, A = ob.agents_view, ob.agents_view.shape[0], net.A
+        io = bufs.get(N)
+        if io is None:
+            dev = view.device
+            io = bufs[N] = dict(obs=torch.zeros(N, A, net.Fld, device=dev), pos=torch.empty(N, dtype=torch.int32, device=dev),
+                                mask=torch.empty(N, A, net.K, dtype=torch.uint8, device=dev), action=torch.empty(N, A, dtype=torch.int32, device=dev),
+                                logp=torch.empty(N, A, device=dev), value=torch.empty(N, A, device=dev))
+        io["obs"][..., :view.shape[2]].copy_(view)
+        io["pos"].copy_(ob.step_count[:, 0] if ob.step_count.dim() == 2 else ob.step_count)
+        mask = None if ob.action_mask is None else io["mask"].copy_(ob.action_mask)
+        _, keys = agent_sample_keys(key, A)   # key, sample_key = split(key) per agent inside get_actions (decode.py:141)
+        if not stateful:
+            actor_apply_fn(io["obs"], io["pos"], None, keys, io["action"], io["logp"], io["value"], mask=mask)
+            return io["action"].clone(), {}
+        hs = actor_state["hidden_state"]   # advanced IN PLACE (the acting kernel updates the states where they are)
+        actor_apply_fn(io["obs"], io["pos"], (hs[0], hs[1], hs[2]), keys, io["action"], io["logp"], io["value"], mask=mask, tag=f"eval{N}")
+        return io["action"].clone(), {"hidden_state": hs}
 
     return eval_act_fn
 

@@ -63,6 +63,14 @@ class FfActor(TorsoNet):
         self.wg_ws = torch.empty(max(self.L.call("magpo_wgrad_workspace_floats", k, n, self.G) for k, n in shapes), device=device)
         self.refresh()
 
+    def _twin_kw(self):
+        return dict(wgrad_groups=self.G, tuning=self.tuning, obs_ld=self.Fld, torso=self.spec)
+
+    def twin(self):
+        """A second network of the same class, shape, row stride and torso on the same device, sharing this one's ``Tuning`` object, with
+        buffers of its own and uninitialised parameters (see GruActor.twin)."""
+        return type(self)(self.A, self.K, self.F, self.dev, **self._twin_kw())
+
     def bind_grads(self, grads: torch.Tensor) -> None:
         """Make ``grads`` (flat, P.numel floats, e.g. a slice of the learner's all-reduce message) the gradient buffer."""
         assert grads.numel() == self.P.numel
@@ -159,6 +167,9 @@ class FfCritic(FfActor):
         global-state rows (num_agents * raw features, stride critic.global_state_ld)."""
         self.centralised = bool(centralised)
         super().__init__(n_agents, 1, obs_dim, device, wgrad_groups=wgrad_groups, seed=seed, grads=grads, tuning=tuning, obs_ld=obs_ld, torso=torso)
+
+    def twin(self):
+        return type(self)(self.A, self.F, self.dev, centralised=self.centralised, **self._twin_kw())
 
     def _values(self, logits, name):
         R = logits.shape[0]

@@ -23,7 +23,7 @@ from typing import Callable, List, Optional
 import torch
 
 from .anakin import AnakinLearner, Group, SystemConfig
-from .envs import host_split
+from .envs import agent_sample_keys, host_split
 from .optim import ClipAdam
 from .params import FlatParams, guider_layout
 from .sable import SableGuider
@@ -90,10 +90,7 @@ class FfSableLearner(AnakinLearner):
         key = g.key
         for t in range(self.T):
             ks = host_split(key, 2)
-            key, k = ks[0], ks[1]
-            for i in range(self.A):
-                kk = host_split(k, 2)
-                k, g.keys_host[t, i] = kk[0], kk[1]
+            key, g.keys_host[t] = ks[0], agent_sample_keys(ks[1], self.A)[1]
         g.key = host_split(key, 2)[0]
 
     def _rollout_body(self, g: Group, skeys):

@@ -16,7 +16,6 @@ Groups, set-up, the rollout's graph capture, the gather and the group dispatch o
 """
 from __future__ import annotations
 
-import os
 from typing import Callable, List, Optional
 
 import torch
@@ -27,7 +26,7 @@ from .actor import GruActor
 # import them from the learner
 from .anakin import AdvStats, AnakinLearner, Group, SystemConfig, jax_permutation, setup_env_groups, split_setup_keys  # noqa: F401
 from .envs import (ConnectorEnvBatch, CoordSumConfig, CoordSumEnvBatch, LbfConfig, LbfEnvBatch, MpeConfig, MpeEnvBatch, RwareConfig,  # noqa: F401
-                   RwareEnvBatch, VectorConnectorConfig, host_split, make_env_batch, net_obs, obs_row_stride, prng_key)
+                   RwareEnvBatch, VectorConnectorConfig, agent_sample_keys, host_split, make_env_batch, net_obs, obs_row_stride, prng_key)
 from .optim import ClipAdam
 from .params import FlatParams, actor_layout, guider_layout
 from .sable import SableGuider
@@ -119,7 +118,7 @@ class MagpoLearner(AnakinLearner):
         # layers in front of the GRU / of the first retention run on the distinct rows only.  MAGPO_CLASS_TABLES=0 = dense path.
         # (the tables are read in place by the 64-wide fused kernels: a 128-wide net takes the dense first layers)
         # (... and need the one-hot id in the network input: the class rows are [id | target])
-        self.class_tables = env_cfg.class_tables and os.environ.get("MAGPO_CLASS_TABLES", "1") != "0" and int(embed_dim) <= 64 and self.obs_off == 0
+        self.class_tables = env_cfg.class_tables and self.tuning.class_tables and int(embed_dim) <= 64 and self.obs_off == 0
         self._cls = None
         # the actor's forward / backward run on a second HIP stream next to the guider's (independent until the loss)
         self.overlap_actor = False  # opt-in (bench.py --overlap): ~3 %, but per-kernel timings then include contention
@@ -185,10 +184,7 @@ class MagpoLearner(AnakinLearner):
         key = g.key
         for t in range(T):
             ks = host_split(key, 2)
-            key, k = ks[0], ks[1]
-            for i in range(A):
-                kk = host_split(k, 2)
-                k, tab[t, i] = kk[0], kk[1]
+            key, tab[t] = ks[0], agent_sample_keys(ks[1], A)[1]
         g.key = host_split(key, 2)[0]
 
     def _rollout_body(self, g: EnvGroup, skeys):

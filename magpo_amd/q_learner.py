@@ -135,6 +135,22 @@ class QGroup(Group):
         return sum(t.numel() * t.element_size() for t in self.ring.values() if t is not None)
 
 
+def check_q_limits(env_cfg, L: int, S: int, micro_batches, system_name: str, env_name: Optional[str] = None) -> None:
+    """What the Q learners' kernels serve, stated once for QLearner and for the systems' ``check_supported`` (which names the config's
+    ``env_name`` too): no micro-batches, an env kernel that writes real_next_obs, windows of 2 <= L <= S steps, narrow rows."""
+    if int(micro_batches or 1) != 1:
+        raise NotImplementedError(f"system.micro_batches is not supported by {system_name}")
+    if not ENV_BATCHES[type(env_cfg)].has_real_obs:
+        cls = type(env_cfg).__name__
+        if env_name is None:
+            raise NotImplementedError(f"{system_name} on {cls}: the env kernel does not write real_next_obs (CoordSum and Level-Based Foraging do)")
+        raise NotImplementedError(f"{system_name} on {env_name} ({cls}): the env kernel does not write real_next_obs; CoordSum and Level-Based Foraging do")
+    if L < 2 or L > S:
+        raise NotImplementedError(f"{system_name}: need 2 <= sample_sequence_length <= buffer_size, got {L} and {S}")
+    if env_cfg.num_actions > 32 or env_cfg.obs_dim > 128:
+        raise NotImplementedError("obs_dim <= 128 and action_dim <= 32 required")
+
+
 class QLearner(AnakinLearner):
     n_loss = 3
     SYSTEMS = "rec_iql"
@@ -143,18 +159,10 @@ class QLearner(AnakinLearner):
                  q_net: Optional[GruQNetwork] = None, optim: Optional[ClipAdam] = None, torso=(None, None)):
         """``q_net`` / ``optim``: the online network and its ClipAdam built by the caller (learner_setup); by default the learner builds its own
         from ``net_seed`` (an int, a PRNG key or None) and the torso specs.  The target network is a second object of the same layout."""
-        if int(getattr(sys, "micro_batches", 1) or 1) != 1:
-            raise NotImplementedError(f"system.micro_batches is not supported by {self.SYSTEMS}")
         if not hasattr(env_cfg, "num_actions") or getattr(env_cfg, "continuous", False):
             raise NotImplementedError(f"{self.SYSTEMS}: discrete actions only")
-        if not ENV_BATCHES[type(env_cfg)].has_real_obs:
-            raise NotImplementedError(f"{self.SYSTEMS} on {type(env_cfg).__name__}: the env kernel does not write real_next_obs (CoordSum and "
-                                      "Level-Based Foraging do)")
-        L_, S = int(sys.sample_sequence_length), int(sys.buffer_size)
-        if L_ < 2 or L_ > S:
-            raise NotImplementedError(f"{self.SYSTEMS}: need 2 <= sample_sequence_length <= buffer_size, got {L_} and {S}")
-        if env_cfg.num_actions > 32 or env_cfg.obs_dim > 128:
-            raise NotImplementedError("obs_dim <= 128 and action_dim <= 32 required")
+        S = int(sys.buffer_size)
+        check_q_limits(env_cfg, int(sys.sample_sequence_length), S, getattr(sys, "micro_batches", 1), self.SYSTEMS)
         super().__init__(env_cfg, num_envs, sys, device)
         self.tuning = tuning if tuning is not None else (q_net.tuning if q_net is not None else Tuning.from_env())
         A, K, F = self.A, self.K, self.F

@@ -51,6 +51,7 @@ class SableGuider(NetBase):
         self.memory_type, self.ff = memory_type, memory_type == "ff_sable"
         if self.ff:
             decay_scaling_factor, use_pe = 1.0, False
+        self.decay_scaling_factor, self.use_pe = float(decay_scaling_factor), bool(use_pe)
         if embed_dim not in (16, 32, 64, 128) or n_head not in (1, 2, 4) or n_block < 1 or embed_dim % n_head or 64 // n_head // n_head < 4:
             raise NotImplementedError("gfx950 Sable kernels: embed_dim in {16, 32, 64, 128} (nets narrower than 64 run embedded in the 64-wide "
                                       "kernels, params.WidthEmbedding) and n_head in {1, 2, 4} (SURVEY 8f rank 3)")
@@ -103,6 +104,12 @@ class SableGuider(NetBase):
         self.refresh()
 
     # ------------------------------------------------------------------ plumbing
+    def twin(self):
+        """A second network of the same shape, row stride and memory settings on the same device, sharing this one's ``Tuning`` object, with
+        buffers of its own and uninitialised parameters (see GruActor.twin)."""
+        return type(self)(self.A, self.K, self.F, self.dev, embed_dim=self.EL, n_head=self.nh, n_block=self.nb, decay_scaling_factor=self.decay_scaling_factor,
+                          use_pe=self.use_pe, max_pos=self.npos, wgrad_groups=self.G, tuning=self.tuning, obs_ld=self.Fld, memory_type=self.memory_type)
+
     def bind_grads(self, grads: torch.Tensor) -> None:
         """Make ``grads`` (a flat fp32 buffer of P.numel floats, e.g. a slice of the learner's all-reduce message) the gradient buffer."""
         assert grads.numel() == self.P.numel

@@ -1,15 +1,23 @@
-"""What the system entry files (gpo/anakin/rec_magpo.py, sable/anakin/rec_sable.py, ppo/anakin/rec_ppo.py) share: reading the config tree,
-the check that get_learner_fn's callables belong to objects that own device buffers, ``learn(state)`` around a learner object, the parts
-of a learner state every system has (rollout state of the env groups, optimiser state), the first and last lines of ``learner_setup`` /
-``run_experiment`` and the experiment loop.  Each system file keeps what is its own: its networks, parameter dicts, hidden states and its
-LearnerState type.
+"""What the ten system entry files share: reading the config tree, the refusals several of them state (``check_action_space``), the check
+that get_learner_fn's callables belong to objects that own device buffers, ``learn(state)`` around a learner object, the parts of a learner
+state every system has (rollout state of the env groups, optimiser state), the first and last lines of ``learner_setup`` /
+``run_experiment``, the experiment loop and ``hydra_entry_point``'s body.  Each system file keeps what is its own:
+
+    gpo/anakin/rec_magpo.py                 guider and GRU actor, both optimisers, Sable and policy hidden states, GPOLearnerState
+    sable/anakin/rec_sable.py, ff_sable.py  the Sable network and its memory settings, (rec) the retention states, the act function that
+                                            executes the network itself (body: evaluator.sable_eval_act_fn)
+    ppo/anakin/rec_ppo.py, ff_ppo.py        behind rec_ippo / rec_mappo and ff_ippo / ff_mappo; what the pairs share is ppo/anakin/ppo_common.py:
+                                            rec adds hidden states and recurrent_chunk_size, ff its torso rule and action-space check
+    q_learning/anakin/rec_iql.py            Q network, replay ring and counters in the state, the run_experiment body of both Q systems
+    q_learning/anakin/rec_qmix.py           the mixer: its settings, parameters and Adam moments next to rec_iql's
 """
 from __future__ import annotations
 
 import copy
 import os
+import sys
 import time
-from typing import Any, Dict, List
+from typing import Any, Dict, List, Optional
 
 import numpy as np
 import torch
@@ -17,7 +25,8 @@ import torch
 from magpo_amd import distributed as mdist
 from magpo_amd.actor import GruActor
 from magpo_amd.anakin import SystemConfig
-from magpo_amd.envs import host_split, obs_row_stride
+from magpo_amd.config import compose
+from magpo_amd.envs import host_split
 from magpo_amd.evaluator import get_eval_fn, get_num_eval_envs, make_ff_eval_act_fn, make_rec_eval_act_fn
 from magpo_amd.torso import DEFAULT_TORSO, torso_from_config
 from magpo_amd.types import ExperimentOutput
@@ -44,6 +53,15 @@ def network_torsos(config, which: str):
         return DEFAULT_TORSO, DEFAULT_TORSO
     return (torso_from_config(node.pre_torso) if "pre_torso" in node else DEFAULT_TORSO,
             torso_from_config(node.post_torso) if "post_torso" in node else DEFAULT_TORSO)
+
+
+def check_action_space(config, label: str, tail: str = "") -> None:
+    """Discrete actions only (the masked categorical head, the eps-greedy selector); the reference's continuous heads are not built.
+    ``label`` / ``tail``: the calling system's words in front of and behind the refused value."""
+    kw = config.env.get("kwargs")
+    action_type = "Discrete" if kw is None else str(kw.get("action_type", "Discrete"))
+    if action_type.lower() != "discrete":
+        raise NotImplementedError(f"{label}, got env.kwargs.action_type={action_type}{tail}")
 
 
 def _owner(fn, cls, method: str, what: str):
@@ -79,9 +97,11 @@ def snapshot_rollout_state(groups):
 
 
 def load_rollout_state(groups, key, env_state, timestep, dones) -> None:
-    """Inverse of ``snapshot_rollout_state``, into the groups' (static, graph-captured) buffers; every group takes a copy of ``key``."""
+    """Inverse of ``snapshot_rollout_state``, into the groups' (static, graph-captured) buffers.  ``key``: one key [2], of which every group
+    takes a copy, or a table [groups, 2] with every group's own (the Q learner's groups carry different keys)."""
     if dones.shape[0] != len(groups):
         raise ValueError(f"learner state holds {dones.shape[0]} env groups, the learner {len(groups)}")
+    keys = np.asarray(key, dtype=np.uint32)
     for gi, grp in enumerate(groups):
         for f in grp.env.state_fields:
             getattr(grp.env, f).copy_(env_state[f][gi])
@@ -90,7 +110,7 @@ def load_rollout_state(groups, key, env_state, timestep, dones) -> None:
             grp.traj["mask"][0].copy_(timestep["action_mask"][gi])
         grp.traj["step_count"][0].copy_(timestep["step_count"][gi])
         grp.traj["done"][0].copy_(dones[gi])
-        grp.key = np.array(key, dtype=np.uint32).copy()
+        grp.key = (keys if keys.ndim == 1 else keys[gi]).copy()
 
 
 def snapshot_opt_state(opt) -> Dict[str, Any]:
@@ -158,24 +178,33 @@ def start_experiment(_config, system_name: str):
     return config, rank, world, torch.device("cuda", local)
 
 
-def train_and_evaluate_gru_actor(config, env, eval_env, learn, actor_network, learner_state, key, key_e, device, rank, world) -> float:
-    """``train_and_evaluate`` for a system whose evaluated policy is a GruActor (rec_magpo, rec_ippo, rec_mappo): the evaluator runs a
-    second actor object of the same torso on its own batch of envs, with the pre-interval ``params.actor_params``."""
-    eval_actor = GruActor(env.num_agents, env.action_dim, env.obs_dim, device, obs_ld=obs_row_stride(env.cfg.obs_dim),
-                          pre_torso=actor_network.pre_spec, post_torso=actor_network.post_spec)
-    return train_and_evaluate(config, env, eval_env, learn, learner_state, make_rec_eval_act_fn(eval_actor, config), key, key_e, device, rank, world,
-                              init_act_state=lambda batch: {"hidden_state": torch.zeros(batch * env.num_agents, 128, device=device)},
+def entry_point(name: str, run_experiment, done_message: str, overrides: Optional[List[str]] = None) -> float:
+    """The body of every ``hydra_entry_point``: compose configs/default/<name>.yaml + CLI overrides, run, print the system's last line."""
+    cfg = compose(name, sys.argv[1:] if overrides is None else overrides)
+    perf = run_experiment(cfg)
+    print(done_message)
+    return perf
+
+
+def zero_gru_state(env, device):
+    """``init_act_state`` of an evaluator whose network carries a GRU state: {"hidden_state": zeros [batch * A, 128]}."""
+    return lambda batch: {"hidden_state": torch.zeros(batch * env.num_agents, 128, device=device)}
+
+
+def train_and_evaluate_actor(config, env, eval_env, learn, actor_network, learner_state, key, key_e, device, rank, world) -> float:
+    """``train_and_evaluate`` for a system whose evaluated policy is a GruActor (rec_magpo, rec_ippo, rec_mappo) or an FfActor (ff_ippo,
+    ff_mappo): the evaluator runs the actor's ``twin()`` on its own batch of envs, with the pre-interval ``params.actor_params``; a
+    feed-forward actor's state is ``{}``."""
+    eval_actor = actor_network.twin()
+    if isinstance(eval_actor, GruActor):
+        act_fn, init_act_state = make_rec_eval_act_fn(eval_actor, config), zero_gru_state(env, device)
+    else:
+        act_fn, init_act_state = make_ff_eval_act_fn(eval_actor, config), lambda batch: {}
+    return train_and_evaluate(config, env, eval_env, learn, learner_state, act_fn, key, key_e, device, rank, world, init_act_state=init_act_state,
                               eval_params=lambda state: state.params.actor_params)
 
 
-def train_and_evaluate_ff_actor(config, env, eval_env, learn, actor_network, learner_state, key, key_e, device, rank, world) -> float:
-    """``train_and_evaluate`` for a system whose evaluated policy is an FfActor (ff_ippo, ff_mappo): a second actor object of the same torso
-    on the evaluator's own batch of envs, with the pre-interval ``params.actor_params``; the actor state is ``{}``."""
-    from magpo_amd.ff_nets import FfActor
-    eval_actor = FfActor(env.num_agents, env.action_dim, env.obs_dim, device, obs_ld=obs_row_stride(env.cfg.obs_dim), torso=actor_network.spec,
-                         tuning=actor_network.tuning)
-    return train_and_evaluate(config, env, eval_env, learn, learner_state, make_ff_eval_act_fn(eval_actor, config), key, key_e, device, rank, world,
-                              init_act_state=lambda batch: {}, eval_params=lambda state: state.params.actor_params)
+train_and_evaluate_gru_actor = train_and_evaluate_ff_actor = train_and_evaluate_actor   # (the names from before the two were one)
 
 
 def train_and_evaluate(config, env, eval_env, learn, learner_state, eval_act_fn, key, key_e, device, rank, world, *, init_act_state, eval_params,

@@ -14,8 +14,6 @@ Multi-GPU: launch one process per GPU with torch.distributed.run; ``n_devices`` 
 """
 from __future__ import annotations
 
-import os
-import sys
 from typing import List, Optional
 
 import numpy as np
@@ -23,13 +21,13 @@ import torch
 
 from magpo_amd import distributed as mdist
 from magpo_amd.actor import GruActor
-from magpo_amd.config import compose
 from magpo_amd.learner import MagpoLearner, host_split, obs_row_stride, prng_key
 from magpo_amd.optim import ClipAdam
 from magpo_amd.sable import SableGuider, load_sable_hstates, sable_hstates_logical
-from magpo_amd.systems.common import (_owner, _system_config, as_dict, load_opt_state, load_rollout_state, make_learner_fn, network_torsos,
-                                      setup_learner, snapshot_opt_state, snapshot_rollout_state, start_experiment,
-                                      train_and_evaluate_gru_actor)
+from magpo_amd.systems.common import (_owner, _system_config, as_dict, entry_point, load_opt_state, load_rollout_state, make_learner_fn,
+                                      network_torsos, setup_learner, snapshot_opt_state, snapshot_rollout_state, start_experiment,
+                                      train_and_evaluate_actor)
+from magpo_amd.tuning import Tuning
 from magpo_amd.types import GPOLearnerState, HiddenStates, OptStates, Params, SableHiddenStates
 from magpo_amd.utils import make_env as environments
 
@@ -133,13 +131,14 @@ def learner_setup(env, keys, config, device=None, rank: int = 0, world: int = 1)
     # parameters = what flax creates from net_key / actor_net_key (rec_magpo.py:598-604,623; magpo_amd/params.py, UNPINNED restatement)
     obs_ld = obs_row_stride(cfg.obs_dim)   # floats between the rows the env kernels write; env.obs_dim = the features the networks read (add_agent_id)
     g_seed, a_seed = np.asarray(net_key, np.uint32), np.asarray(actor_net_key, np.uint32)
-    if os.environ.get("MAGPO_LEGACY_INIT") == "1":   # A/B only: the torch-generator initialisation of rounds 1-3 (same distributions, other draws)
+    tuning = Tuning.from_env()   # ONE object shared by both networks (tuning.py)
+    if tuning.legacy_init:   # A/B only: the torch-generator initialisation of rounds 1-3 (same distributions, other draws)
         g_seed = int(net_key[1]) & 0x7FFFFFFF
         a_seed = g_seed + 1
     sable_network = SableGuider(cfg.num_agents, cfg.num_actions, env.obs_dim, device, obs_ld=obs_ld, embed_dim=int(nc.embed_dim), n_head=int(nc.n_head),
                                 n_block=int(nc.n_block), decay_scaling_factor=float(mc.decay_scaling_factor),
-                                use_pe=bool(mc.timestep_positional_encoding), max_pos=cfg.time_limit + 1, seed=g_seed)
-    actor_network = GruActor(cfg.num_agents, cfg.num_actions, env.obs_dim, device, obs_ld=obs_ld, seed=a_seed, tuning=sable_network.tuning,
+                                use_pe=bool(mc.timestep_positional_encoding), max_pos=cfg.time_limit + 1, seed=g_seed, tuning=tuning)
+    actor_network = GruActor(cfg.num_agents, cfg.num_actions, env.obs_dim, device, obs_ld=obs_ld, seed=a_seed, tuning=tuning,
                              pre_torso=pre_torso, post_torso=post_torso)
     guider_optim, actor_optim = ClipAdam(sable_network, sysc), ClipAdam(actor_network, sysc)
     # Pack apply and update functions (rec_magpo.py:624-632)
@@ -156,15 +155,12 @@ def run_experiment(_config) -> float:
     ks = host_split(prng_key(int(config.system.seed)), 4)
     key, key_e, actor_net_key, net_key = ks[0], ks[1], ks[2], ks[3]
     learn, actor_network, learner_state = learner_setup(env, (key, actor_net_key, net_key), config, device, rank, world)
-    return train_and_evaluate_gru_actor(config, env, eval_env, learn, actor_network, learner_state, key, key_e, device, rank, world)
+    return train_and_evaluate_actor(config, env, eval_env, learn, actor_network, learner_state, key, key_e, device, rank, world)
 
 
 def hydra_entry_point(overrides: Optional[List[str]] = None) -> float:
     """Experiment entry point (rec_magpo.py:818-831): compose configs/default/rec_magpo.yaml + CLI overrides."""
-    cfg = compose("rec_magpo", sys.argv[1:] if overrides is None else overrides)
-    perf = run_experiment(cfg)
-    print("MAGPO experiment completed")
-    return perf
+    return entry_point("rec_magpo", run_experiment, "MAGPO experiment completed", overrides)
 
 
 if __name__ == "__main__":

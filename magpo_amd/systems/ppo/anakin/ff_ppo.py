@@ -10,8 +10,6 @@ Anything else raises NotImplementedError at set-up.
 """
 from __future__ import annotations
 
-import dataclasses
-import sys
 from types import SimpleNamespace
 from typing import List, Optional
 
@@ -19,23 +17,17 @@ import numpy as np
 import torch
 
 from magpo_amd import distributed as mdist
-from magpo_amd.config import compose
-from magpo_amd.critic import global_state_ld
 from magpo_amd.ff_nets import FF_DEFAULT_TORSO, FfActor, FfCritic
 from magpo_amd.ff_ppo_learner import FfPpoLearner
-from magpo_amd.learner import SystemConfig, host_split, obs_row_stride, prng_key
+from magpo_amd.learner import host_split, obs_row_stride, prng_key
 from magpo_amd.optim import ClipAdam
-from magpo_amd.ppo_learner import LOSS_NAMES, raw_features
-from magpo_amd.systems.common import (_owner, _system_config, as_dict, load_opt_state, load_rollout_state, make_learner_fn, setup_learner,
-                                      snapshot_opt_state, snapshot_rollout_state, start_experiment, train_and_evaluate_ff_actor)
-from magpo_amd.systems.ppo.types import LearnerState, OptStates, Params
+from magpo_amd.ppo_learner import LOSS_NAMES
+from magpo_amd.systems import common
+from magpo_amd.systems.common import entry_point, make_learner_fn, setup_learner, start_experiment, train_and_evaluate_actor
+from magpo_amd.systems.ppo.anakin.ppo_common import critic_input, critic_system_config, load_shared, owners, snapshot_shared, system_config  # noqa: F401
+from magpo_amd.systems.ppo.types import LearnerState
 from magpo_amd.torso import torso_from_config
 from magpo_amd.utils import make_env as environments
-
-
-def system_config(config) -> SystemConfig:
-    """The learner's settings from an ff_ippo / ff_mappo config tree (no ``clip_gpo`` / ``alpha``: MAGPO's keys, never read here)."""
-    return _system_config(config, clip_gpo=SystemConfig.clip_gpo, alpha=SystemConfig.alpha)
 
 
 def network_torso(config, which: str):
@@ -51,29 +43,18 @@ def network_torso(config, which: str):
 
 def check_action_space(config) -> None:
     """Discrete actions only (the masked categorical head); the reference's continuous head (TanhTransformedDistribution) is not built."""
-    kw = config.env.get("kwargs")
-    action_type = "Discrete" if kw is None else str(kw.get("action_type", "Discrete"))
-    if action_type.lower() != "discrete":
-        raise NotImplementedError(f"ff_ippo / ff_mappo support discrete action spaces only (DiscreteActionHead), got env.kwargs.action_type={action_type}; "
-                                  "continuous actions are not implemented")
+    common.check_action_space(config, "ff_ippo / ff_mappo support discrete action spaces only (DiscreteActionHead)",
+                              "; continuous actions are not implemented")
 
 
 def _snapshot_state(learner: FfPpoLearner) -> LearnerState:
     """LearnerState of the learner as an independent COPY (ff_mappo.py:264); leaves carry a leading group axis."""
-    gs = learner.groups
-    params = Params({k: v.clone() for k, v in learner.actor.named.items()}, {k: v.clone() for k, v in learner.critic.named.items()})
-    return LearnerState(params, OptStates(snapshot_opt_state(learner.a_opt), snapshot_opt_state(learner.c_opt)), gs[0].key.copy(),
-                        *snapshot_rollout_state(gs))
+    return LearnerState(*snapshot_shared(learner))
 
 
 def load_learner_state(learner: FfPpoLearner, state: LearnerState) -> None:
     """Inverse of ``_snapshot_state``: write every leaf of ``state`` into the learner's (static, graph-captured) buffers."""
-    params, opts = as_dict(state.params), as_dict(state.opt_states)
-    learner.actor.load_named(params["actor_params"])
-    learner.critic.load_named(params["critic_params"])
-    load_opt_state(learner.a_opt, opts["actor_opt_state"])
-    load_opt_state(learner.c_opt, opts["critic_opt_state"])
-    load_rollout_state(learner.groups, state.key, state.env_state, state.timestep, state.dones)
+    load_shared(learner, state)
 
 
 def make_system(name: str, centralised: bool) -> SimpleNamespace:
@@ -88,16 +69,7 @@ def make_system(name: str, centralised: bool) -> SimpleNamespace:
         Under the rule of rec_sable.get_learner_fn: the callables must be the bound methods ``FfActor.apply`` / ``FfCritic.apply`` and
         ``ClipAdam.update`` of the objects that own the device buffers (or thin functools.wraps / functools.partial adaptors around them),
         and the loop CALLS exactly what it is given; anything else raises the ``TypeError`` of common._owner."""
-        actor_apply_fn, critic_apply_fn = apply_fns
-        actor_update_fn, critic_update_fn = update_fns
-        critic = _owner(critic_apply_fn, FfCritic, "apply", "apply_fns[1] (critic_apply_fn)")
-        actor = _owner(actor_apply_fn, FfActor, "apply", "apply_fns[0] (actor_apply_fn)")
-        if isinstance(actor, FfCritic):
-            raise TypeError("get_learner_fn: apply_fns[0] (actor_apply_fn) must belong to an FfActor, not to the critic")
-        a_opt = _owner(actor_update_fn, ClipAdam, "update", "update_fns[0] (actor_update_fn)")
-        c_opt = _owner(critic_update_fn, ClipAdam, "update", "update_fns[1] (critic_update_fn)")
-        if a_opt.net is not actor or c_opt.net is not critic:
-            raise ValueError("update_fns must be the update functions of the optimisers of (actor, critic), in this order")
+        actor, critic, a_opt, c_opt = owners(apply_fns, update_fns, FfActor, FfCritic, "an FfActor")
         _, world = mdist.rank_world()
         learner = FfPpoLearner(env.cfg, int(config.arch.num_envs), a_opt.sys, actor.dev, centralised=centralised,
                                num_groups=int(config.system.update_batch_size), actor=actor, critic=critic, optims=(a_opt, c_opt),
@@ -112,14 +84,10 @@ def make_system(name: str, centralised: bool) -> SimpleNamespace:
         check_action_space(config)
         device = device or torch.device("cuda", torch.cuda.current_device())
         cfg, sysc = env.cfg, system_config(config)
-        csys = dataclasses.replace(sysc, actor_lr=float(config.system.critic_lr))   # ClipAdam reads its rate as actor_lr
+        csys = critic_system_config(sysc, config)
         obs_ld = obs_row_stride(cfg.obs_dim)
         a_torso, c_torso = network_torso(config, "actor_network"), network_torso(config, "critic_network")
-        if centralised:   # observation.global_state: the raw views of all agents (the same limit and message as rec_mappo)
-            cF = cfg.num_agents * raw_features(cfg)
-            cld = global_state_ld(cfg.num_agents, raw_features(cfg))
-        else:
-            cF, cld = env.obs_dim, obs_ld
+        cF, cld = critic_input(env, centralised)
         # parameters = what flax creates from actor_net_key / critic_net_key (ff_mappo.py:311-312; UNPINNED restatement, magpo_amd/params.py)
         actor_network = FfActor(cfg.num_agents, cfg.num_actions, env.obs_dim, device, obs_ld=obs_ld, seed=np.asarray(actor_net_key, np.uint32),
                                 torso=a_torso)
@@ -140,14 +108,11 @@ def make_system(name: str, centralised: bool) -> SimpleNamespace:
         ks = host_split(prng_key(int(config.system.seed)), 4)
         key, key_e, actor_net_key, critic_net_key = ks[0], ks[1], ks[2], ks[3]
         learn, actor_network, learner_state = learner_setup(env, (key, actor_net_key, critic_net_key), config, device, rank, world)
-        return train_and_evaluate_ff_actor(config, env, eval_env, learn, actor_network, learner_state, key, key_e, device, rank, world)
+        return train_and_evaluate_actor(config, env, eval_env, learn, actor_network, learner_state, key, key_e, device, rank, world)
 
     def hydra_entry_point(overrides: Optional[List[str]] = None) -> float:
         """Experiment entry point (ff_mappo.py:513-526): compose configs/default/<system>.yaml + CLI overrides."""
-        cfg = compose(name, sys.argv[1:] if overrides is None else overrides)
-        perf = run_experiment(cfg)
-        print(f"{'MAPPO' if centralised else 'IPPO'} experiment completed")
-        return perf
+        return entry_point(name, run_experiment, f"{'MAPPO' if centralised else 'IPPO'} experiment completed", overrides)
 
     return SimpleNamespace(get_learner_fn=get_learner_fn, learner_setup=learner_setup, run_experiment=run_experiment,
                            hydra_entry_point=hydra_entry_point)

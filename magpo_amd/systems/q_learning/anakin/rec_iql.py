@@ -9,21 +9,20 @@ Supported envs: CoordSum and Level-Based Foraging, whose step kernels write real
 """
 from __future__ import annotations
 
-import sys
-from typing import List, Optional
+from typing import Callable, List, Optional
 
 import numpy as np
 import torch
 
 from magpo_amd import distributed as mdist
-from magpo_amd.config import compose
-from magpo_amd.envs import ENV_BATCHES, host_split, obs_row_stride, prng_key
+from magpo_amd.envs import host_split, obs_row_stride, prng_key
 from magpo_amd.evaluator import make_q_eval_act_fn
 from magpo_amd.optim import ClipAdam
-from magpo_amd.q_learner import LOSS_NAMES, QLearner, QSystemConfig, epsilon
+from magpo_amd.q_learner import LOSS_NAMES, QLearner, QSystemConfig, check_q_limits, epsilon
 from magpo_amd.q_net import GruQNetwork
-from magpo_amd.systems.common import (_owner, as_dict, load_opt_state, make_learner_fn, network_torsos, snapshot_opt_state, start_experiment,
-                                      train_and_evaluate)
+from magpo_amd.systems.common import (_owner, as_dict, check_action_space, entry_point, load_opt_state, load_rollout_state, make_learner_fn,
+                                      network_torsos, setup_learner, snapshot_opt_state, snapshot_rollout_state, start_experiment,
+                                      train_and_evaluate, zero_gru_state)
 from magpo_amd.systems.q_learning.types import LearnerState, QNetParams
 from magpo_amd.utils import make_env as environments
 
@@ -39,38 +38,24 @@ def system_config(config) -> QSystemConfig:
                          lr_num_updates=int(s.num_updates) if s.get("num_updates") else 1000)
 
 
-def check_supported(env_cfg, config) -> None:
-    """What rec_iql refuses, before any device work."""
-    kw = config.env.get("kwargs")
-    action_type = "Discrete" if kw is None else str(kw.get("action_type", "Discrete"))
-    if action_type.lower() != "discrete":
-        raise NotImplementedError(f"rec_iql supports discrete action spaces only, got env.kwargs.action_type={action_type}")
-    if int(config.system.get("micro_batches", 1) or 1) != 1:
-        raise NotImplementedError("system.micro_batches is not supported by rec_iql")
+def check_supported(env_cfg, config, name: str = NAME) -> None:
+    """What rec_iql (or the system ``name`` built on it) refuses, before any device work."""
+    check_action_space(config, f"{name} supports discrete action spaces only")
     if int(config.network.hidden_state_dim) != 128:
         raise NotImplementedError("HIP kernels support hidden_state_dim=128")
-    if not ENV_BATCHES[type(env_cfg)].has_real_obs:
-        raise NotImplementedError(f"rec_iql on {config.env.env_name} ({type(env_cfg).__name__}): the env kernel does not write real_next_obs; CoordSum "
-                                  "and Level-Based Foraging do")
-    L_, S = int(config.system.sample_sequence_length), int(config.system.buffer_size)
-    if L_ < 2 or L_ > S:
-        raise NotImplementedError(f"rec_iql: need 2 <= sample_sequence_length <= buffer_size, got {L_} and {S}")
-    if env_cfg.num_actions > 32 or env_cfg.obs_dim > 128:
-        raise NotImplementedError("obs_dim <= 128 and action_dim <= 32 required")
+    check_q_limits(env_cfg, int(config.system.sample_sequence_length), int(config.system.buffer_size), config.system.get("micro_batches", 1), name,
+                   env_name=config.env.env_name)
 
 
 def _snapshot_state(learner: QLearner) -> LearnerState:
     """LearnerState of the learner as an independent COPY (rec_iql.py:464-476); leaves carry a leading group axis."""
     gs = learner.groups
     st = lambda f: torch.stack([f(g) for g in gs])
-    obs = dict(agents_view=st(lambda g: g.traj["obs"][0]), step_count=st(lambda g: g.traj["step_count"][0]))
-    if gs[0].traj["mask"] is not None:
-        obs["action_mask"] = st(lambda g: g.traj["mask"][0])
-    env_state = {f: st(lambda g: getattr(g.env, f)) for f in gs[0].env.state_fields}
+    env_state, obs, term_or_trunc = snapshot_rollout_state(gs)
     buffer_state = dict(experience={k: st(lambda g: g.ring[k]) for k, v in gs[0].ring.items() if v is not None},
                         current_index=st(lambda g: g.cursor[0]), filled=st(lambda g: g.filled[0]))
     params = QNetParams({k: v.clone() for k, v in learner.q_net.named.items()}, {k: v.clone() for k, v in learner.target_net.named.items()})
-    return LearnerState(obs, st(lambda g: g.term[0]), st(lambda g: g.traj["done"][0]), st(lambda g: g.h[0]), env_state, st(lambda g: g.t_dev[0]),
+    return LearnerState(obs, st(lambda g: g.term[0]), term_or_trunc, st(lambda g: g.h[0]), env_state, st(lambda g: g.t_dev[0]),
                         torch.full((len(gs),), learner.t_train, dtype=torch.int32, device=learner.dev), snapshot_opt_state(learner.q_opt), buffer_state,
                         params, np.stack([g.key for g in gs]).astype(np.uint32))
 
@@ -78,21 +63,13 @@ def _snapshot_state(learner: QLearner) -> LearnerState:
 def load_learner_state(learner: QLearner, state: LearnerState) -> None:
     """Inverse of ``_snapshot_state``: write every leaf of ``state`` into the learner's (static, graph-captured) buffers."""
     params, buf = as_dict(state.params), state.buffer_state
-    if state.terminal.shape[0] != len(learner.groups):
-        raise ValueError(f"learner state holds {state.terminal.shape[0]} env groups, the learner {len(learner.groups)}")
+    keys = np.asarray(state.key, np.uint32).reshape(-1, 2)     # one key per group
+    load_rollout_state(learner.groups, keys, state.env_state, state.obs, state.term_or_trunc)
     learner.q_net.load_named(params["online"])
     learner.target_net.load_named(params["target"])
     load_opt_state(learner.q_opt, state.opt_state)
-    keys = np.asarray(state.key, np.uint32).reshape(len(learner.groups), 2)
     for gi, g in enumerate(learner.groups):
-        for f in g.env.state_fields:
-            getattr(g.env, f).copy_(state.env_state[f][gi])
-        g.traj["obs"][0].copy_(state.obs["agents_view"][gi])
-        g.traj["step_count"][0].copy_(state.obs["step_count"][gi])
-        if g.traj["mask"] is not None:
-            g.traj["mask"][0].copy_(state.obs["action_mask"][gi])
         g.term[0].copy_(state.terminal[gi])
-        g.traj["done"][0].copy_(state.term_or_trunc[gi])
         g.h[0].copy_(state.hidden_state[gi])
         for k, v in g.ring.items():
             if v is not None:
@@ -103,7 +80,6 @@ def load_learner_state(learner: QLearner, state: LearnerState) -> None:
         g.adds = g.t // learner.N            # one stored step per env step of the group
         if (g.adds % g.S, min(g.adds, g.S)) != (int(buf["current_index"][gi]), int(buf["filled"][gi])):
             raise ValueError("learner state: the buffer's counters do not belong to its time_steps")
-        g.key = keys[gi].copy()
     learner.t_train = int(state.train_steps[0])
     learner.t_train_dev.fill_(learner.t_train)
 
@@ -135,38 +111,35 @@ def learner_setup(env, keys, config, device=None, rank: int = 0, world: int = 1)
                             pre_torso=pre, post_torso=post)
     q_optim = ClipAdam(q_network, sysc)
     learn = get_learner_fn(env, q_network.apply, q_optim.update, config)
-    learner = learn.learner
-    U = len(learner.groups)
-    learner.setup(key, n_groups=world * U, group=rank * U)
-    learner._live_state = _snapshot_state(learner)
-    return learn, q_network, learner._live_state
+    return learn, q_network, setup_learner(learn, key, _snapshot_state, rank, world)
+
+
+def run_q_experiment(_config, name: str, add_global_state: bool, learner_setup: Callable) -> float:
+    """``run_experiment`` of rec_iql (rec_iql.py:492-618) and rec_qmix (rec_qmix.py:550-680): they differ in the name, in ``add_global_state``
+    of the env factory and in the module's ``learner_setup``.  Evaluation acts greedily on the online Q network's ``twin()``."""
+    config, rank, world, device = start_experiment(_config, name)
+    env, eval_env = environments.make(config, add_global_state=add_global_state)
+    ks = host_split(prng_key(int(config.system.seed)), 2)    # key, q_key = split(key) (:86)
+    key, q_key = ks[0], ks[1]
+    learn, _, learner_state = learner_setup(env, (key, q_key), config, device, rank, world)
+    ks = host_split(learn.learner.setup_key, 2)              # key, eval_key = split(key) (:514)
+    key, key_e = ks[0], ks[1]
+    eval_net = learn.learner.q_net.twin()
+    s = config.system
+    # num_updates update steps of rollout_length env steps like every Anakin system here (check_total_timesteps)
+    return train_and_evaluate(config, env, eval_env, learn, learner_state, make_q_eval_act_fn(eval_net, config), key, key_e, device, rank, world,
+                              init_act_state=zero_gru_state(env, device), eval_params=lambda state: state.params.online,
+                              misc_metrics=lambda t: {"epsilon": epsilon(t, float(s.eps_min), float(s.eps_decay))})
 
 
 def run_experiment(_config) -> float:
     """Runs experiment (rec_iql.py:492-618)."""
-    config, rank, world, device = start_experiment(_config, NAME)
-    env, eval_env = environments.make(config)
-    ks = host_split(prng_key(int(config.system.seed)), 2)    # key, q_key = split(key) (:86)
-    key, q_key = ks[0], ks[1]
-    learn, q_network, learner_state = learner_setup(env, (key, q_key), config, device, rank, world)
-    ks = host_split(learn.learner.setup_key, 2)              # key, eval_key = split(key) (:514)
-    key, key_e = ks[0], ks[1]
-    eval_net = GruQNetwork(env.num_agents, env.action_dim, env.obs_dim, device, obs_ld=obs_row_stride(env.cfg.obs_dim), pre_torso=q_network.pre_spec,
-                           post_torso=q_network.post_spec)
-    s = config.system
-    # rec_iql runs num_updates update steps of rollout_length env steps like every Anakin system here (check_total_timesteps)
-    return train_and_evaluate(config, env, eval_env, learn, learner_state, make_q_eval_act_fn(eval_net, config), key, key_e, device, rank, world,
-                              init_act_state=lambda batch: {"hidden_state": torch.zeros(batch * env.num_agents, 128, device=device)},
-                              eval_params=lambda state: state.params.online,
-                              misc_metrics=lambda t: {"epsilon": epsilon(t, float(s.eps_min), float(s.eps_decay))})
+    return run_q_experiment(_config, NAME, False, learner_setup)
 
 
 def hydra_entry_point(overrides: Optional[List[str]] = None) -> float:
     """Experiment entry point (rec_iql.py:621-637): compose configs/default/rec_iql.yaml + CLI overrides."""
-    cfg = compose(NAME, sys.argv[1:] if overrides is None else overrides)
-    perf = run_experiment(cfg)
-    print("IDQN experiment completed")
-    return perf
+    return entry_point(NAME, run_experiment, "IDQN experiment completed", overrides)
 
 
 if __name__ == "__main__":

@@ -10,27 +10,22 @@ Supported: what rec_iql supports (CoordSum and Level-Based Foraging), a global s
 """
 from __future__ import annotations
 
-import sys
 from typing import List, Optional
 
 import numpy as np
 import torch
 
 from magpo_amd import distributed as mdist
-from magpo_amd.config import compose
-from magpo_amd.envs import host_split, obs_row_stride, prng_key
-from magpo_amd.evaluator import make_q_eval_act_fn
+from magpo_amd.envs import obs_row_stride
 from magpo_amd.optim import ClipAdam
 from magpo_amd.ppo_learner import raw_features
-from magpo_amd.q_learner import epsilon
 from magpo_amd.q_net import GruQNetwork
 from magpo_amd.qmix_learner import LOSS_NAMES, QmixLearner, adam_alone
 from magpo_amd.qmix_net import QMixer, check_mixer_shape
-from magpo_amd.systems.common import _owner, as_dict, make_learner_fn, network_torsos, start_experiment, train_and_evaluate
+from magpo_amd.systems.common import _owner, as_dict, entry_point, make_learner_fn, network_torsos, setup_learner
 from magpo_amd.systems.q_learning.anakin import rec_iql
 from magpo_amd.systems.q_learning.anakin.rec_iql import system_config
 from magpo_amd.systems.q_learning.types import LearnerState, QMIXParams
-from magpo_amd.utils import make_env as environments
 
 NAME = "rec_qmix"
 MIXER_TARGET = "mava.networks.base.QMixingNetwork"
@@ -46,10 +41,7 @@ def mixer_settings(config):
 
 def check_supported(env_cfg, config) -> None:
     """What rec_qmix refuses, before any device work: what rec_iql refuses, and what the mixer kernels do not serve."""
-    try:
-        rec_iql.check_supported(env_cfg, config)
-    except NotImplementedError as e:
-        raise NotImplementedError(str(e).replace("rec_iql", NAME)) from None
+    rec_iql.check_supported(env_cfg, config, NAME)
     mx = config.network.get("mixer_network")
     target = MIXER_TARGET if mx is None else str(mx.get("_target_", MIXER_TARGET))
     if target != MIXER_TARGET:
@@ -110,37 +102,17 @@ def learner_setup(env, keys, config, device=None, rank: int = 0, world: int = 1)
     E, _, norm = mixer_settings(config)
     mixer = QMixer(cfg.num_agents, E, raw_features(cfg), device, id_cols=cfg.num_agents, norm_env_states=norm, seed=q_key)
     learn = get_learner_fn(env, (q_network.apply, mixer.apply), (adam_alone(q_network, sysc).update, adam_alone(mixer, sysc).update), config)
-    learner = learn.learner
-    U = len(learner.groups)
-    learner.setup(key, n_groups=world * U, group=rank * U)
-    learner._live_state = _snapshot_state(learner)
-    return learn, (q_network, mixer), learner._live_state
+    return learn, (q_network, mixer), setup_learner(learn, key, _snapshot_state, rank, world)
 
 
 def run_experiment(_config) -> float:
     """Runs experiment (rec_qmix.py:550-680)."""
-    config, rank, world, device = start_experiment(_config, NAME)
-    env, eval_env = environments.make(config, add_global_state=True)
-    ks = host_split(prng_key(int(config.system.seed)), 2)    # key, q_key = split(key, 2) (:88)
-    key, q_key = ks[0], ks[1]
-    learn, (q_network, _), learner_state = learner_setup(env, (key, q_key), config, device, rank, world)
-    ks = host_split(learn.learner.setup_key, 2)
-    key, key_e = ks[0], ks[1]
-    eval_net = GruQNetwork(env.num_agents, env.action_dim, env.obs_dim, device, obs_ld=obs_row_stride(env.cfg.obs_dim), pre_torso=q_network.pre_spec,
-                           post_torso=q_network.post_spec)
-    s = config.system
-    return train_and_evaluate(config, env, eval_env, learn, learner_state, make_q_eval_act_fn(eval_net, config), key, key_e, device, rank, world,
-                              init_act_state=lambda batch: {"hidden_state": torch.zeros(batch * env.num_agents, 128, device=device)},
-                              eval_params=lambda state: state.params.online,
-                              misc_metrics=lambda t: {"epsilon": epsilon(t, float(s.eps_min), float(s.eps_decay))})
+    return rec_iql.run_q_experiment(_config, NAME, True, learner_setup)
 
 
 def hydra_entry_point(overrides: Optional[List[str]] = None) -> float:
     """Experiment entry point (rec_qmix.py:683-699): compose configs/default/rec_qmix.yaml + CLI overrides."""
-    cfg = compose(NAME, sys.argv[1:] if overrides is None else overrides)
-    perf = run_experiment(cfg)
-    print("QMIX experiment completed")
-    return perf
+    return entry_point(NAME, run_experiment, "QMIX experiment completed", overrides)
 
 
 if __name__ == "__main__":

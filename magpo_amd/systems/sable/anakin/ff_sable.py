@@ -15,19 +15,19 @@ Supported: discrete action spaces, all five environments, ``memory_config.agents
 """
 from __future__ import annotations
 
-import sys
-from typing import Callable, Dict, List, Optional
+from typing import Callable, List, Optional
 
 import numpy as np
 import torch
 
 from magpo_amd import distributed as mdist
-from magpo_amd.config import compose
+from magpo_amd.evaluator import sable_eval_act_fn
 from magpo_amd.ff_sable_learner import LOSS_NAMES, FfSableLearner
 from magpo_amd.learner import SystemConfig, host_split, obs_row_stride, prng_key
 from magpo_amd.optim import ClipAdam
 from magpo_amd.sable import SableGuider
-from magpo_amd.systems.common import (_owner, _system_config, load_opt_state, load_rollout_state, make_learner_fn, setup_learner,
+from magpo_amd.systems import common
+from magpo_amd.systems.common import (_owner, _system_config, entry_point, load_opt_state, load_rollout_state, make_learner_fn, setup_learner,
                                       snapshot_opt_state, snapshot_rollout_state, start_experiment, train_and_evaluate)
 from magpo_amd.systems.sable.types import FFLearnerState, Transition  # noqa: F401
 from magpo_amd.types import ExperimentOutput  # noqa: F401
@@ -43,10 +43,7 @@ def system_config(config) -> SystemConfig:
 
 def check_action_space(config) -> None:
     """Discrete actions only; the reference's continuous head is not built."""
-    kw = config.env.get("kwargs")
-    action_type = "Discrete" if kw is None else str(kw.get("action_type", "Discrete"))
-    if action_type.lower() != "discrete":
-        raise NotImplementedError(f"ff_sable supports discrete action spaces only, got env.kwargs.action_type={action_type}")
+    common.check_action_space(config, "ff_sable supports discrete action spaces only")
 
 
 def configure_memory(config, num_agents: int) -> None:
@@ -142,35 +139,7 @@ def make_ff_sable_eval_act_fn(actor_apply_fn: Callable) -> Callable:
     net = _owner(actor_apply_fn, SableGuider, "act", "actor_apply_fn")
     if not net.ff:
         raise ValueError("make_ff_sable_eval_act_fn needs a SableGuider with memory_type='ff_sable'")
-    loaded = {"params": None}
-    bufs: Dict[int, Dict[str, torch.Tensor]] = {}
-
-    def eval_act_fn(params: Optional[Dict[str, torch.Tensor]], timestep, key: np.ndarray, actor_state):
-        if params is not None and params is not net.named and params is not loaded["params"]:
-            net.load_named(params)
-            loaded["params"] = params
-        ob = timestep.observation
-        view, N, A = ob.agents_view, ob.agents_view.shape[0], net.A
-        io = bufs.get(N)
-        if io is None:
-            dev = view.device
-            io = bufs[N] = dict(obs=torch.zeros(N, A, net.Fld, device=dev), pos=torch.empty(N, dtype=torch.int32, device=dev),
-                                mask=torch.empty(N, A, net.K, dtype=torch.uint8, device=dev), action=torch.empty(N, A, dtype=torch.int32, device=dev),
-                                logp=torch.empty(N, A, device=dev), value=torch.empty(N, A, device=dev))
-        io["obs"][..., :view.shape[2]].copy_(view)
-        io["pos"].copy_(ob.step_count[:, 0] if ob.step_count.dim() == 2 else ob.step_count)
-        mask = None
-        if ob.action_mask is not None:
-            mask = io["mask"].copy_(ob.action_mask)
-        keys = np.zeros((A, 2), np.uint32)   # key, sample_key = split(key) per agent inside get_actions (decode.py:141)
-        k = np.asarray(key, dtype=np.uint32).reshape(2)
-        for i in range(A):
-            kk = host_split(k, 2)
-            k, keys[i] = kk[0], kk[1]
-        actor_apply_fn(io["obs"], io["pos"], None, keys, io["action"], io["logp"], io["value"], mask=mask)
-        return io["action"].clone(), {}
-
-    return eval_act_fn
+    return sable_eval_act_fn(net, actor_apply_fn, stateful=False)
 
 
 def run_experiment(_config) -> float:
@@ -182,19 +151,14 @@ def run_experiment(_config) -> float:
     learn, sable_execution_fn, learner_state = learner_setup(env, (key, net_key), config, device, rank, world)
 
     # the evaluator runs the Sable network on its own batch of envs, with the pre-interval parameters: a second network object
-    train_net = learn.learner.guider
-    eval_net = SableGuider(train_net.A, train_net.K, train_net.F, device, obs_ld=train_net.Fld, embed_dim=train_net.EL, n_head=train_net.nh,
-                           n_block=train_net.nb, memory_type="ff_sable", max_pos=train_net.npos, tuning=train_net.tuning)
+    eval_net = learn.learner.guider.twin()
     return train_and_evaluate(config, env, eval_env, learn, learner_state, make_ff_sable_eval_act_fn(acting_fn(eval_net)), key, key_e, device, rank, world,
                               init_act_state=lambda batch: {}, eval_params=lambda state: state.params)
 
 
 def hydra_entry_point(overrides: Optional[List[str]] = None) -> float:
     """Experiment entry point (ff_sable.py:559-573): compose configs/default/ff_sable.yaml + CLI overrides."""
-    cfg = compose("ff_sable", sys.argv[1:] if overrides is None else overrides)
-    perf = run_experiment(cfg)
-    print("FF Sable experiment completed")
-    return perf
+    return entry_point("ff_sable", run_experiment, "FF Sable experiment completed", overrides)
 
 
 if __name__ == "__main__":

@@ -12,20 +12,19 @@ helpers are the ones every system uses (magpo_amd/systems/common.py, magpo_amd/s
 """
 from __future__ import annotations
 
-import sys
-from typing import Callable, Dict, List, Optional
+from typing import Callable, List, Optional
 
 import numpy as np
 import torch
 
 from magpo_amd import distributed as mdist
-from magpo_amd.config import compose
+from magpo_amd.evaluator import sable_eval_act_fn
 from magpo_amd.learner import SystemConfig, host_split, obs_row_stride, prng_key
 from magpo_amd.optim import ClipAdam
 from magpo_amd.sable import SableGuider, load_sable_hstates, sable_hstates_logical
 from magpo_amd.sable_learner import LOSS_NAMES, SableLearner
-from magpo_amd.systems.common import (_owner, _system_config, as_dict, load_opt_state, load_rollout_state, make_learner_fn, setup_learner,
-                                      snapshot_opt_state, snapshot_rollout_state, start_experiment, train_and_evaluate)
+from magpo_amd.systems.common import (_owner, _system_config, as_dict, entry_point, load_opt_state, load_rollout_state, make_learner_fn,
+                                      setup_learner, snapshot_opt_state, snapshot_rollout_state, start_experiment, train_and_evaluate)
 from magpo_amd.systems.sable.types import HiddenStates, LearnerState, Transition  # noqa: F401
 from magpo_amd.types import ExperimentOutput  # noqa: F401
 from magpo_amd.utils import make_env as environments
@@ -128,38 +127,7 @@ def make_rec_sable_act_fn(actor_apply_fn: Callable) -> Callable:
     the tensors of the same dict in place and passes it again evaluates the previously loaded weights -- pass a new dict (a learner
     state snapshot is one) or ``net.named`` itself."""
     net = _owner(actor_apply_fn, SableGuider, "get_actions", "actor_apply_fn")
-    loaded = {"params": None}
-    bufs: Dict[int, Dict[str, torch.Tensor]] = {}
-    _hidden_state = "hidden_state"
-
-    def eval_act_fn(params: Optional[Dict[str, torch.Tensor]], timestep, key: np.ndarray, actor_state):
-        if params is not None and params is not net.named and params is not loaded["params"]:
-            net.load_named(params)
-            loaded["params"] = params
-        ob = timestep.observation
-        view, N, A = ob.agents_view, ob.agents_view.shape[0], net.A
-        io = bufs.get(N)
-        if io is None:   # the kernel's inputs and outputs for this batch size, allocated once (the acting kernel caches its pointer tables)
-            dev = view.device
-            io = bufs[N] = dict(obs=torch.zeros(N, A, net.Fld, device=dev), pos=torch.empty(N, dtype=torch.int32, device=dev),
-                                mask=torch.empty(N, A, net.K, dtype=torch.uint8, device=dev), action=torch.empty(N, A, dtype=torch.int32, device=dev),
-                                logp=torch.empty(N, A, device=dev), value=torch.empty(N, A, device=dev))
-        io["obs"][..., :view.shape[2]].copy_(view)
-        io["pos"].copy_(ob.step_count[:, 0] if ob.step_count.dim() == 2 else ob.step_count)
-        mask = None
-        if ob.action_mask is not None:
-            mask = io["mask"].copy_(ob.action_mask)
-        hs = actor_state[_hidden_state]   # advanced IN PLACE (the acting kernel updates the states where they are)
-        # key, sample_key = split(key) per agent inside get_actions (decode.py:141)
-        keys = np.zeros((A, 2), np.uint32)
-        k = np.asarray(key, dtype=np.uint32).reshape(2)
-        for i in range(A):
-            kk = host_split(k, 2)
-            k, keys[i] = kk[0], kk[1]
-        actor_apply_fn(io["obs"], io["pos"], (hs[0], hs[1], hs[2]), keys, io["action"], io["logp"], io["value"], mask=mask, tag=f"eval{N}")
-        return io["action"].clone(), {_hidden_state: hs}
-
-    return eval_act_fn
+    return sable_eval_act_fn(net, actor_apply_fn, stateful=True)
 
 
 def run_experiment(_config) -> float:
@@ -171,10 +139,7 @@ def run_experiment(_config) -> float:
     learn, sable_execution_fn, learner_state = learner_setup(env, (key, net_key), config, device, rank, world)
 
     # the evaluator runs the Sable network on its own batch of envs, with the pre-interval parameters: a second network object
-    train_net = learn.learner.guider
-    eval_net = SableGuider(train_net.A, train_net.K, train_net.F, device, obs_ld=train_net.Fld, embed_dim=train_net.EL, n_head=train_net.nh,
-                           n_block=train_net.nb, decay_scaling_factor=float(config.network.memory_config.decay_scaling_factor),
-                           use_pe=bool(config.network.memory_config.timestep_positional_encoding), max_pos=train_net.npos, tuning=train_net.tuning)
+    eval_net = learn.learner.guider.twin()
     eval_act_fn = make_rec_sable_act_fn(eval_net.get_actions)
     return train_and_evaluate(config, env, eval_env, learn, learner_state, eval_act_fn, key, key_e, device, rank, world,
                               init_act_state=lambda batch: {"hidden_state": get_init_hidden_state(eval_net, batch)},
@@ -183,10 +148,7 @@ def run_experiment(_config) -> float:
 
 def hydra_entry_point(overrides: Optional[List[str]] = None) -> float:
     """Experiment entry point (rec_sable.py:623-636): compose configs/default/rec_sable.yaml + CLI overrides."""
-    cfg = compose("rec_sable", sys.argv[1:] if overrides is None else overrides)
-    perf = run_experiment(cfg)
-    print("Rec Sable experiment completed")
-    return perf
+    return entry_point("rec_sable", run_experiment, "Rec Sable experiment completed", overrides)
 
 
 if __name__ == "__main__":

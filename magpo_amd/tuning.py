@@ -27,6 +27,10 @@ Environment variables are read HERE, once, when the default instance is built (A
     MAGPO_FF_SABLE_FUSED_ACT=0|1  acting step of ff_sable: 1 = encoder, value head, the A decoder iterations and the sampling in one magpo_ff_sable_act
                                 launch (csrc/ff_sable_act.hip, SableGuider.act_team_fused), 0 = the kernel-by-kernel chain SableGuider.act.  Same function;
                                 the one launch is the more accurate and, as measured, the slower of the two: default 0
+    MAGPO_CLASS_TABLES=0        MagpoLearner: the first layers on the dense path, not on the class tables of the distinct input rows (csrc/classtab.hip,
+                                DESIGN 4b); default 1 = tables wherever the environment and the network width allow them
+    MAGPO_LEGACY_INIT=1         rec_magpo.learner_setup, A/B only: the torch-generator initialisation of rounds 1-3 (same distributions, other draws)
+                                instead of the parameters flax creates from the net keys
 """
 from __future__ import annotations
 
@@ -49,6 +53,8 @@ class Tuning:
     dense_bwd_min_rows: int = 16384   # NetBase.dense_bwd: rows from which a narrow dense layer's dW and dX come from one magpo_dense_bwd launch (64 x 256:
                                       # the size from which magpo_wgrad uses its whole-matrix kernels); below it the pair magpo_wgrad + magpo_linear.  No
                                       # environment variable: tests set the field
+    class_tables: bool = True     # MagpoLearner.class_tables: first-layer class tables where env and network allow them (False: dense path)
+    legacy_init: bool = False     # rec_magpo.learner_setup: the torch-generator initialisation (A/B only)
 
     @classmethod
     def from_env(cls, env=None) -> "Tuning":
@@ -65,4 +71,6 @@ class Tuning:
         t.ff_fused_step = e["MAGPO_FF_FUSED_STEP"] == "1" if e.get("MAGPO_FF_FUSED_STEP") in ("0", "1") else cls().ff_fused_step
         t.ff_sable_fused_act = (e["MAGPO_FF_SABLE_FUSED_ACT"] == "1" if e.get("MAGPO_FF_SABLE_FUSED_ACT") in ("0", "1")
                                 else cls().ff_sable_fused_act)
+        t.class_tables = e.get("MAGPO_CLASS_TABLES", "1") != "0"
+        t.legacy_init = e.get("MAGPO_LEGACY_INIT") == "1"
         return t

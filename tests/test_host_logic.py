@@ -271,6 +271,27 @@ def test_tuning_defaults_and_environment_switches():
     assert o.linear_variant & 4 and o.actor_linear_variant & 4 and o.wgrad_variant & 64 and o.gru_split_bf16 == 1 and o.ret_chunk_tokens == 64
     e = Tuning.from_env({"MAGPO_LINEAR_BF3": "", "MAGPO_GRU_SPLIT_BF16": ""})                         # empty variables = unset
     assert e == Tuning()
+    # the two product-path switches that are fields like the others: class tables (on) and the legacy initialisation (off)
+    assert d.class_tables is True and d.legacy_init is False
+    assert Tuning.from_env({"MAGPO_CLASS_TABLES": "0"}).class_tables is False and Tuning.from_env({"MAGPO_CLASS_TABLES": "1"}).class_tables is True
+    assert Tuning.from_env({"MAGPO_LEGACY_INIT": "1"}).legacy_init is True and Tuning.from_env({"MAGPO_LEGACY_INIT": "0"}).legacy_init is False
+
+
+@pytest.mark.parametrize("A", [1, 3])
+def test_agent_sample_keys_is_the_per_agent_split_chain(A):
+    """envs.agent_sample_keys: key, sample_key = split(key) once per agent in agent order (decode.py:141), against the explicit loop over
+    the oracle's split; the carried key is the loop's."""
+    from magpo_amd.envs import agent_sample_keys
+    from oracle import prng
+    key = prng.split(prng.prng_key(1234), 3)[2]
+    k, want = key, []
+    for _ in range(A):
+        k, sample_key = prng.split(k, 2)
+        want.append(sample_key)
+    carried, keys = agent_sample_keys(key, A)
+    assert keys.dtype == np.uint32 and keys.shape == (A, 2) and carried.dtype == np.uint32 and carried.shape == (2,)
+    assert np.array_equal(keys, np.stack(want)) and np.array_equal(carried, k)
+    assert not np.array_equal(carried, key) and np.array_equal(key, prng.split(prng.prng_key(1234), 3)[2])   # the input key is not written
 
 
 def test_net_obs_column_offsets_for_add_agent_id_false():

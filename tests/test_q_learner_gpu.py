@@ -175,6 +175,30 @@ def test_learn_is_a_function_of_its_state_and_checkpoints_resume(tmp_path):
         assert torch.equal(a, b), "resumed run differs from the uninterrupted one"
 
 
+def test_groups_with_different_keys_round_trip_through_snapshot_and_load(tmp_path):
+    """common.load_rollout_state with a [groups, 2] key table (the Q learner keeps one key per group; the other systems pass one key for
+    all): every group gets its own row back, as a copy, and a single key still goes to every group."""
+    from magpo_amd.systems.common import load_rollout_state
+    from magpo_amd.systems.q_learning.anakin import rec_iql
+    learn, _, s0 = _setup(_small_cfg(tmp_path, 11, ["system.update_batch_size=2"]))
+    learner = learn.learner
+    assert s0.key.shape == (2, 2) and not np.array_equal(s0.key[0], s0.key[1])      # setup gave the groups different keys
+    s1 = learn(s0).learner_state
+    assert not np.array_equal(s1.key[0], s1.key[1]) and not np.array_equal(s1.key, s0.key)
+    rec_iql.load_learner_state(learner, s0)
+    for gi, g in enumerate(learner.groups):
+        assert g.key.dtype == np.uint32 and np.array_equal(g.key, s0.key[gi]) and not np.shares_memory(g.key, s0.key)
+    back = rec_iql._snapshot_state(learner)
+    assert np.array_equal(back.key, s0.key)
+    for a, b in zip(_flat(back), _flat(s0)):
+        assert torch.equal(a, b)
+    swapped = s0._replace(key=s0.key[::-1].copy())                                    # the rows follow the group axis, not a fixed order
+    rec_iql.load_learner_state(learner, swapped)
+    assert np.array_equal(learner.groups[0].key, s0.key[1]) and np.array_equal(learner.groups[1].key, s0.key[0])
+    load_rollout_state(learner.groups, s0.key[1], s0.env_state, s0.obs, s0.term_or_trunc)   # one key: a copy for every group
+    assert all(np.array_equal(g.key, s0.key[1]) for g in learner.groups) and not np.shares_memory(learner.groups[0].key, learner.groups[1].key)
+
+
 @pytest.mark.parametrize("env", ["lbf", "coordsum"])
 def test_hydra_entry_point_trains_and_evaluates(env, tmp_path):
     from magpo_amd.systems.q_learning.anakin import rec_iql
