@@ -13,11 +13,10 @@ from typing import Optional
 
 import contextlib
 
-import numpy as np
 import torch
 
 from .netbase import TorsoNet
-from .params import FlatParams, actor_layout, actor_named_views, init_actor, init_actor_from_key
+from .params import actor_layout, actor_named_views, init_actor, init_actor_from_key
 from .torso import DEFAULT_TORSO, TorsoSpec, layer_name
 from .tuning import Tuning
 
@@ -39,28 +38,15 @@ class GruActor(TorsoNet):
         self.pre_spec = pre_torso if pre_torso is not None else DEFAULT_TORSO
         self.post_spec = post_torso if post_torso is not None else DEFAULT_TORSO
         self.Dpre, self.Dpost = self.pre_spec.width, self.post_spec.width
-        # first pre-torso layer on narrow observations: the small-input kernels serve Dense(F->128)+ReLU without LayerNorm; any other first
-        # layer reads the observations as a zero-padded [R][64] operand (magpo_small_operand) through magpo_linear / magpo_wgrad
-        p0 = self.pre_spec
-        self.small_first = not self.wide and p0.layer_sizes[0] == 128 and p0.act(0) == 1 and not p0.use_layer_norm
-        self.KP = 128 if self.wide else 64    # columns of the first layer's (padded) operand
-        self.P = FlatParams(actor_layout(obs_dim, H, action_dim, self.pre_spec, self.post_spec), device)
-        self.grads = torch.zeros_like(self.P.flat) if grads is None else grads
-        assert self.grads.numel() == self.P.numel
-        self.v = self.P.views()
-        self.gv = self.P.views(self.grads)
-        self.named = actor_named_views(self.v)
-        self.named_grads = actor_named_views(self.gv)
-        if isinstance(seed, np.ndarray):   # a PRNG key: the parameters flax creates from it (rec_magpo.py:623; params.init_actor_from_key)
-            init_actor_from_key(self.named, seed)
-        elif seed is not None:
-            init_actor(self.named, seed)
+        self._set_first_layer(self.pre_spec)
+        self._bind_params(actor_layout(obs_dim, H, action_dim, self.pre_spec, self.post_spec), actor_named_views, grads)
+        self._init_params(seed, init_actor_from_key, init_actor)   # (a key: rec_magpo.py:623)
         shapes = [(H, 3 * H), (self.Dpre, 3 * H), (self.Dpost, self.K)]   # every (KIN, NOUT) of a weight gradient
         for spec, din in ((self.pre_spec, self.KP), (self.post_spec, H)):
             for d in spec.layer_sizes:
                 shapes.append((din, d))
                 din = d
-        self.wg_ws = torch.empty(max(self.L.call("magpo_wgrad_workspace_floats", k, n, self.G) for k, n in shapes), device=device)
+        self._size_wgrad_ws(shapes)
         self.refresh()
 
     def _twin_kw(self):
@@ -73,32 +59,14 @@ class GruActor(TorsoNet):
         process environment, so sharing the object gives a system's evaluation network the values a fresh default would have.)"""
         return type(self)(self.A, self.K, self.F, self.dev, **self._twin_kw())
 
-    def bind_grads(self, grads: torch.Tensor) -> None:
-        """Make ``grads`` (flat, P.numel floats, e.g. a slice of the learner's all-reduce message) the gradient buffer."""
-        assert grads.numel() == self.P.numel
-        self.grads = grads
-        self.gv = self.P.views(self.grads)
-        self.named_grads = actor_named_views(self.gv)
-
-    def load_named(self, params):
-        with torch.no_grad():
-            for n, v in self.named.items():
-                v.copy_(params[n].to(self.dev, torch.float32).reshape(v.shape))
-        self.refresh()
-
     def refresh(self):
         v = self.v
-        if not self.small_first:   # W_pre [F, D0] as [D0][KP] with zero columns beyond F
-            if "pre" not in self.wt:
-                self.wt["pre"] = torch.zeros(self.pre_spec.layer_sizes[0], self.KP, device=self.dev)
-            self.wt["pre"][:, :self.F].copy_(v["pre.kernel"].t())
         self._tp("wi", v["gru.wi"]); self._tp("wh", v["gru.wh"])
         for prefix, spec in (("pre", self.pre_spec), ("post", self.post_spec)):
             for i in range(1 if prefix == "pre" else 0, len(spec.layer_sizes)):
                 n = layer_name(prefix, i)
                 self._tp(n, v[n + ".kernel"])
-        ht = self._tp("head", v["head.kernel"], 64)      # [64][D_post]
-        self._tp("head_nat_pad", ht, self.Dpost)          # [D_post][64]
+        self._refresh_first_and_head(self.pre_spec, self.Dpost)
         # W_i with its gate columns in the order of the backward scan's gradient matrix (n | r | z), see seq_bwd
         if "wi_nrz" not in self.wt:
             self.wt["wi_nrz"] = torch.empty(self.Dpre, 3 * H, device=self.dev)

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from .netbase import TorsoNet
-from .params import FlatParams, ff_layout, init_ff, init_ff_from_key
+from .params import ff_layout, init_ff, init_ff_from_key
 from .torso import ACT_CODES, TorsoSpec, layer_name
 from .tuning import Tuning
 
@@ -43,24 +43,15 @@ class FfActor(TorsoNet):
         self.A, self.K = n_agents, action_dim
         self.spec = torso if torso is not None else FF_DEFAULT_TORSO
         self.D = self.spec.width
-        s0 = self.spec
-        self.small_first = not self.wide and s0.layer_sizes[0] == 128 and s0.act(0) == 1 and not s0.use_layer_norm   # see netbase.TorsoNet
-        self.KP = 128 if self.wide else 64
-        self.P = FlatParams(ff_layout(obs_dim, action_dim, self.spec), device)
-        self.grads = torch.zeros_like(self.P.flat) if grads is None else grads
-        assert self.grads.numel() == self.P.numel
-        self.v = self.P.views()
-        self.gv = self.P.views(self.grads)
-        self.named, self.named_grads = dict(self.v), dict(self.gv)
-        if isinstance(seed, np.ndarray):
-            init_ff_from_key(self.named, seed, self.HEAD_PATH, self.HEAD_GAIN)
-        elif seed is not None:
-            init_ff(self.named, seed, self.HEAD_GAIN)
+        self._set_first_layer(self.spec)
+        self._bind_params(ff_layout(obs_dim, action_dim, self.spec), grads=grads)   # the layout's names are the reference's
+        self._init_params(seed, lambda named, key: init_ff_from_key(named, key, self.HEAD_PATH, self.HEAD_GAIN),
+                          lambda named, s: init_ff(named, s, self.HEAD_GAIN))
         shapes, din = [(self.D, self.K)], self.KP
         for d in self.spec.layer_sizes:
             shapes.append((din, d))
             din = d
-        self.wg_ws = torch.empty(max(self.L.call("magpo_wgrad_workspace_floats", k, n, self.G) for k, n in shapes), device=device)
+        self._size_wgrad_ws(shapes)
         self.refresh()
 
     def _twin_kw(self):
@@ -71,30 +62,11 @@ class FfActor(TorsoNet):
         buffers of its own and uninitialised parameters (see GruActor.twin)."""
         return type(self)(self.A, self.K, self.F, self.dev, **self._twin_kw())
 
-    def bind_grads(self, grads: torch.Tensor) -> None:
-        """Make ``grads`` (flat, P.numel floats, e.g. a slice of the learner's all-reduce message) the gradient buffer."""
-        assert grads.numel() == self.P.numel
-        self.grads = grads
-        self.gv = self.P.views(self.grads)
-        self.named_grads = dict(self.gv)
-
-    def load_named(self, params):
-        with torch.no_grad():
-            for n, v in self.named.items():
-                v.copy_(params[n].to(self.dev, torch.float32).reshape(v.shape))
-        self.refresh()
-
     def refresh(self):
         """Derived weight copies: the transposed layers of magpo_linear, which are also the images magpo_mlp_act_step reads."""
-        v = self.v
-        if not self.small_first:   # W_0 [F, D0] as [D0][KP] with zero columns beyond F
-            if "pre" not in self.wt:
-                self.wt["pre"] = torch.zeros(self.spec.layer_sizes[0], self.KP, device=self.dev)
-            self.wt["pre"][:, :self.F].copy_(v["pre.kernel"].t())
         for i in range(1, len(self.spec.layer_sizes)):
-            self._tp(layer_name("pre", i), v[layer_name("pre", i) + ".kernel"])
-        ht = self._tp("head", v["head.kernel"], 64)      # [64][D]
-        self._tp("head_nat_pad", ht, self.D)             # [D][64]
+            self._tp(layer_name("pre", i), self.v[layer_name("pre", i) + ".kernel"])
+        self._refresh_first_and_head(self.spec, self.D)
 
     # ------------------------------------------------------------------ composed forward (training, and acting with the fused step off)
     def _rows(self, obs) -> int:

@@ -1,6 +1,7 @@
 """Host-side plumbing shared by the networks (SableGuider, GruActor, FfActor): named workspaces, transposed weight copies, the dense-layer
 and weight-gradient launches with the optional side stream, slab reductions and cached device-pointer tables; ``TorsoNet`` adds the forward
-and backward of one MLPTorso for the networks that have one (GruActor / GruCritic, FfActor / FfCritic)."""
+and backward of one MLPTorso for the networks that have one (GruActor / GruCritic, FfActor / FfCritic), the rule for their first layer and the
+derived copies of first layer and head.  ``ParamBinding`` is the flat parameter / gradient buffer with its named views, shared with QMixer."""
 from __future__ import annotations
 
 from typing import Dict, Optional
@@ -9,6 +10,7 @@ import numpy as np
 import torch
 
 from ._lib import lib
+from .params import FlatParams
 from .torso import layer_name
 from .tuning import Tuning
 
@@ -26,7 +28,46 @@ class _Bufs:
         return t
 
 
-class NetBase:
+class ParamBinding:
+    """One flat parameter buffer ``P`` and one flat gradient buffer ``grads`` with views by layout name (``v`` / ``gv``) and by the reference's
+    names (``named`` / ``named_grads``: what the optimiser, the checkpoints and ``load_named`` see).  The class supplies ``dev`` and ``refresh``."""
+
+    def _bind_params(self, layout, named_views=None, grads: Optional[torch.Tensor] = None) -> None:
+        """``named_views``: views by layout name -> views by reference name (default: the same names).  ``grads``: a buffer to bind, else
+        one of its own."""
+        self._named_views = named_views or dict
+        self.P = FlatParams(layout, self.dev)
+        self.v = self.P.views()
+        self.named = self._named_views(self.v)
+        self.bind_grads(torch.zeros_like(self.P.flat) if grads is None else grads)
+
+    def bind_grads(self, grads: torch.Tensor) -> None:
+        """Make ``grads`` (flat, P.numel floats, e.g. a slice of the learner's all-reduce message) the gradient buffer."""
+        assert grads.numel() == self.P.numel
+        self.grads = grads
+        self.gv = self.P.views(grads)
+        self.named_grads = self._named_views(self.gv)
+
+    def _init_params(self, seed, from_key, from_seed) -> None:
+        """``seed``: None (parameters are loaded later), a PRNG key ([2] uint32: ``from_key(named, key)``, the parameters flax creates from
+        it) or an int (``from_seed(named, seed)``, torch generator)."""
+        if isinstance(seed, np.ndarray):
+            from_key(self.named, seed)
+        elif seed is not None:
+            from_seed(self.named, seed)
+
+    def _check_loaded(self) -> None:
+        """Hook of ``load_named``: refuse parameters the kernels do not evaluate."""
+
+    def load_named(self, params) -> None:
+        with torch.no_grad():
+            for n, v in self.named.items():
+                v.copy_(params[n].to(self.dev, torch.float32).reshape(v.shape))
+        self._check_loaded()
+        self.refresh()
+
+
+class NetBase(ParamBinding):
     LINEAR_VARIANT = "linear_variant"   # the Tuning field that picks this network's magpo_linear variant
     MAX_TABLES = 4096                   # cached pointer tables: all are dropped beyond this many
 
@@ -130,10 +171,30 @@ class NetBase:
 
 class TorsoNet(NetBase):
     """NetBase + the MLPTorso forward / backward (magpo_amd/torso.py) on the dense, LayerNorm and small-input kernels.  The network supplies
-    ``v`` / ``gv`` (parameter and gradient views named by ``layer_name``), ``wt`` (transposed copies kept by its ``refresh``), ``wg_ws``, and for
+    ``v`` / ``gv`` (parameter and gradient views named by ``layer_name``) and the further transposed copies in ``wt`` (its ``refresh``).  For
     its ``pre`` torso (the one that reads observation rows) ``small_first`` and ``KP``: the first layer on narrow observations is served by the
     small-input kernels when it is Dense(F->128)+ReLU without LayerNorm; any other first layer reads the observations as a zero-padded
     [R][64] operand (magpo_small_operand) through magpo_linear / magpo_wgrad."""
+
+    def _set_first_layer(self, spec) -> None:
+        """``small_first`` / ``KP`` (columns of the first layer's padded operand) from the torso ``spec`` that reads the observation rows."""
+        self.small_first = not self.wide and spec.layer_sizes[0] == 128 and spec.act(0) == 1 and not spec.use_layer_norm
+        self.KP = 128 if self.wide else 64
+
+    def _size_wgrad_ws(self, shapes) -> None:
+        """The weight-gradient workspace for ``shapes``: every (KIN, NOUT) of a weight gradient of this network."""
+        self.wg_ws = torch.empty(max(self.L.call("magpo_wgrad_workspace_floats", k, n, self.G) for k, n in shapes), device=self.dev)
+
+    def _refresh_first_and_head(self, first_spec, head_in_width) -> None:
+        """Derived copies at both ends: W_pre [F, D0] as [D0][KP] with zero columns beyond F (unless ``small_first``), and the head as
+        [64][D] (forward) and [D][64] (natural, padded to 64 columns: dX of the head)."""
+        v = self.v
+        if not self.small_first:
+            if "pre" not in self.wt:
+                self.wt["pre"] = torch.zeros(first_spec.layer_sizes[0], self.KP, device=self.dev)
+            self.wt["pre"][:, :self.F].copy_(v["pre.kernel"].t())
+        ht = self._tp("head", v["head.kernel"], 64)
+        self._tp("head_nat_pad", ht, head_in_width)
 
     def _torso_fwd(self, prefix, spec, X, ldx, R, ctx):
         """One MLPTorso (torsos.py:36-47) on R rows of X (stride ldx; the pre-torso's X are observation rows of F features).  Buffers are

@@ -14,7 +14,8 @@ import numpy as np
 import torch
 
 from ._lib import lib
-from .params import FlatParams, _orth, _param_key
+from .netbase import ParamBinding
+from .params import _orth, _orthogonal, _param_key
 
 HYPER_HIDDEN = 64
 EMBED_DIMS = (32, 64)
@@ -45,20 +46,30 @@ def check_mixer_shape(A: int, E: int, G: int, hyper_hidden: int = HYPER_HIDDEN) 
         raise NotImplementedError(f"QMIX mixer: the global state has {G} inputs; the kernels read at most {G_MAX}")
 
 
-def init_mixer_from_key(named: Dict[str, torch.Tensor], key: np.ndarray) -> None:
-    """The QMixingNetwork parameters flax creates from ``key`` (rec_qmix.py:144-145), in the manner of params.init_actor_from_key: every
-    Dense kernel orthogonal(sqrt 2) from the key of its module path, zero biases, LayerNorm scale 1 / bias 0.  UNPINNED like the other
-    initialisers."""
+def _init_mixer(named: Dict[str, torch.Tensor], kernel) -> None:
+    """Every Dense kernel from ``kernel(name, view)`` (orthogonal(sqrt 2)), zero biases, LayerNorm scale 1 / bias 0."""
     with torch.no_grad():
         for n, v in named.items():
             if n.endswith("/kernel"):
-                path = tuple(n.split("/")[:-1])
-                v.copy_(torch.from_numpy(np.ascontiguousarray(_orth(_param_key(key, path, 1), tuple(v.shape), math.sqrt(2.0)))))
+                v.copy_(kernel(n, v))
             else:
                 v.fill_(1.0 if n == "layer_norm/scale" else 0.0)
 
 
-class QMixer:
+def init_mixer_from_key(named: Dict[str, torch.Tensor], key: np.ndarray) -> None:
+    """The QMixingNetwork parameters flax creates from ``key`` (rec_qmix.py:144-145), in the manner of params.init_actor_from_key: every
+    Dense kernel from the key of its module path.  UNPINNED like the other initialisers."""
+    _init_mixer(named, lambda n, v: torch.from_numpy(np.ascontiguousarray(
+        _orth(_param_key(key, tuple(n.split("/")[:-1]), 1), tuple(v.shape), math.sqrt(2.0)))))
+
+
+def init_mixer(named: Dict[str, torch.Tensor], seed: int) -> None:
+    """The same distributions from a torch generator."""
+    gen = torch.Generator().manual_seed(int(seed))
+    _init_mixer(named, lambda n, v: _orthogonal(gen, tuple(v.shape), math.sqrt(2.0)))
+
+
+class QMixer(ParamBinding):
     def __init__(self, n_agents: int, embed_dim: int, raw_features: int, device, *, id_cols: int = 0, norm_env_states: bool = True,
                  hyper_hidden: int = HYPER_HIDDEN, seed=None, grads: Optional[torch.Tensor] = None):
         """``raw_features``: width of one raw agent view (G = n_agents * raw_features state inputs); ``id_cols``: leading columns of every
@@ -67,36 +78,13 @@ class QMixer:
         check_mixer_shape(A, E, G, hyper_hidden)
         self.A, self.E, self.G, self.F_raw, self.id_cols, self.norm = A, E, G, int(raw_features), int(id_cols), bool(norm_env_states)
         self.dev, self.L = device, lib()
-        self.P = FlatParams(mixer_layout(A, E, G), device)
-        self.named = self.P.views()
-        self.bind_grads(torch.zeros_like(self.P.flat) if grads is None else grads)
+        self._bind_params(mixer_layout(A, E, G), grads=grads)   # the layout's names are the reference's parameter paths
         names = [e + s for e in ENTRIES for s in ("/kernel", "/bias")] + ["layer_norm/scale", "layer_norm/bias"]
         self.offs = np.array([self.P.offsets[n] for n in names], dtype=np.int64)
         self.SV = int(self.L.raw("magpo_qmix_save_floats")(E, G))
         self._buf: Dict[str, torch.Tensor] = {}
         self._saved = None
-        if isinstance(seed, np.ndarray):
-            init_mixer_from_key(self.named, seed)
-        elif seed is not None:
-            gen = torch.Generator().manual_seed(int(seed))
-            from .params import _orthogonal
-            with torch.no_grad():
-                for n, v in self.named.items():
-                    if n.endswith("/kernel"):
-                        v.copy_(_orthogonal(gen, tuple(v.shape), math.sqrt(2.0)))
-                    else:
-                        v.fill_(1.0 if n == "layer_norm/scale" else 0.0)
-
-    def bind_grads(self, grads: torch.Tensor) -> None:
-        assert grads.numel() == self.P.numel
-        self.grads = grads
-        self.named_grads = self.P.views(grads)
-
-    def load_named(self, params) -> None:
-        with torch.no_grad():
-            for n, v in self.named.items():
-                v.copy_(params[n].to(self.dev, torch.float32).reshape(v.shape))
-        self.refresh()
+        self._init_params(seed, init_mixer_from_key, init_mixer)
 
     def refresh(self) -> None:
         """The kernels read the parameter buffer itself: nothing is derived from it."""

@@ -18,6 +18,7 @@ I, J with the 128 x 128 state kept as four 64 x 64 tiles S[I][J] (exact: retenti
 from __future__ import annotations
 
 import math
+from functools import partial
 from typing import Dict, Optional, Tuple
 
 import numpy as np
@@ -71,23 +72,19 @@ class SableGuider(NetBase):
         self.kappa = self.kappas[0]
         # P / grads: the LOGICAL parameters (optimiser, all-reduce, checkpoints); PD / grads_D: what the kernels read and write.
         # For embed_dim = 64 they are the same buffers.
-        self.P = FlatParams(guider_layout(self.EL, obs_dim, action_dim, self.nb, self.nh), device)
-        self.grads = torch.zeros_like(self.P.flat) if grads is None else grads
-        assert self.grads.numel() == self.P.numel
         if self.EL == E:
-            self.emb, self.PD, self.grads_D = None, self.P, self.grads
+            self.emb = None
         else:
             self.emb = WidthEmbedding(self.EL, obs_dim, action_dim, self.nb, self.nh, device)
             self.PD = FlatParams(guider_layout(E, obs_dim, action_dim, self.nb, self.nh), device)
             self.grads_D = torch.zeros_like(self.PD.flat)
-        self.v = self.PD.views()
-        self.gv = self.PD.views(self.grads_D)
-        self.named = guider_named_views(self.P.views(), self.EL, self.nh)
-        self.named_grads = guider_named_views(self.P.views(self.grads), self.EL, self.nh)
-        if isinstance(seed, np.ndarray):   # a PRNG key: the parameters flax creates from it (rec_magpo.py:598-604; params.init_guider_from_key)
-            init_guider_from_key(self.named, seed, self.EL, self.nh)
-        elif seed is not None:
-            init_guider(self.named, seed, self.EL)
+        self._bind_params(guider_layout(self.EL, obs_dim, action_dim, self.nb, self.nh), lambda views: guider_named_views(views, self.EL, self.nh), grads)
+        if self.emb is None:
+            self.PD = self.P
+        else:
+            self.v = self.PD.views()
+        self._init_params(seed, lambda named, key: init_guider_from_key(named, key, self.EL, self.nh),   # (a key: rec_magpo.py:598-604)
+                          lambda named, s: init_guider(named, s, self.EL))
         self.npos = max_pos
         self.pe = torch.zeros(max_pos, E, device=device)
         if use_pe:
@@ -111,25 +108,20 @@ class SableGuider(NetBase):
                           use_pe=self.use_pe, max_pos=self.npos, wgrad_groups=self.G, tuning=self.tuning, obs_ld=self.Fld, memory_type=self.memory_type)
 
     def bind_grads(self, grads: torch.Tensor) -> None:
-        """Make ``grads`` (a flat fp32 buffer of P.numel floats, e.g. a slice of the learner's all-reduce message) the gradient buffer."""
-        assert grads.numel() == self.P.numel
-        self.grads = grads
+        """The LOGICAL gradient buffer; the kernels write ``grads_D`` -- the same buffer, or the embedded network's own, which train_bwd
+        folds into ``grads``."""
+        super().bind_grads(grads)
         if self.emb is None:
             self.grads_D = grads
-        self.gv = self.PD.views(self.grads_D)
-        self.named_grads = guider_named_views(self.P.views(self.grads), self.EL, self.nh)
+        else:
+            self.gv = self.PD.views(self.grads_D)
 
     def check_ffn_zero(self):
         for n, v in self.v.items():
             if ".ffn." in n and bool(v.any().item()):
                 raise NotImplementedError("non-zero SwiGLU weights: the FFN branch is not evaluated by the HIP path")
 
-    def load_named(self, params: Dict[str, torch.Tensor]):
-        with torch.no_grad():
-            for n, v in self.named.items():
-                v.copy_(params[n].to(self.dev, torch.float32).reshape(v.shape))
-        self.check_ffn_zero()
-        self.refresh()
+    _check_loaded = check_ffn_zero   # load_named's hook
 
     def refresh(self):
         """Rebuild the device parameters (embed_dim < 64), the transposed (forward-GEMM) weight copies and the acting kernel's
@@ -239,136 +231,83 @@ class SableGuider(NetBase):
 
     # ------------------------------------------------------------------ retention helpers (per state tile)
     def _tiles(self):
-        """State tiles of one retention layer as (tile, q / k column offset, v / r column offset, width, kappa): one per head, or -- one
-        128-wide head -- the four 64 x 64 blocks S[I][J] (q, k columns of half I meet v, r columns of half J; outputs add over I)."""
+        """State tiles of one retention layer as (tile, q / k column offset, v / r column offset, width, kappa, first_v, first_qk): one per
+        head, or -- one 128-wide head -- the four 64 x 64 blocks S[I][J] (q, k columns of half I meet v, r columns of half J).  Results for
+        the v / r columns add over I and those for the q / k columns over J: ``first_v`` / ``first_qk`` say whether the tile is the first
+        to write them (one tile per head: always)."""
         if self.blockwise:
-            return [(2 * i + j, TILE * i, TILE * j, TILE, self.kappas[0]) for i in (0, 1) for j in (0, 1)]
-        return [(h, h * self.hs, h * self.hs, self.hs, self.kappas[h]) for h in range(self.nh)]
+            return [(2 * i + j, TILE * i, TILE * j, TILE, self.kappas[0], i == 0, j == 0) for i in (0, 1) for j in (0, 1)]
+        return [(h, h * self.hs, h * self.hs, self.hs, self.kappas[h], True, True) for h in range(self.nh)]
 
     def add_rows(self, dst, ldd, src, lds, R, W):
         self.L.call("magpo_add_rows", dst, ldd, src, lds, R, W, self._st())
 
+    def _tile_launch(self, launch, R, *outs):
+        """One tile's ``launch(dst, ld, ...)`` with a (dst, ld) pair per entry (dst, ld, first, temporary's name) of ``outs``: the first
+        tile to write these columns writes them in place, a later one goes to the [R, 64] temporary, which is then added."""
+        tgt = [(dst, ld) if first else (self.b.get(tmp, (R, TILE)), TILE) for dst, ld, first, tmp in outs]
+        launch(*(x for t in tgt for x in t))
+        for (dst, ld, first, _), (t, _) in zip(outs, tgt):
+            if not first:
+                self.add_rows(dst, ld, t, TILE, R, TILE)
+
     def _ret_rec(self, S, q, ldq, k, ldk, v, ldv, env_rows, u, ldu, N, ntok, ret_from, write, gp, ldg, gamma, beta):
-        """Recurrent retention + GroupNorm / gate for every state tile; S [ntile, N, 64, 64].  Rows: token a of env e at e * env_rows + a.
-        ff_sable: the same rows from the stateless team kernel (S, write unused; the rows of an env are consecutive)."""
-        E = self.E
-        if self.ff:
-            assert env_rows == self.A
-            return self._team_ret_act(q, ldq, k, ldk, v, ldv, u, ldu, N, ntok, ret_from, gp, ldg, gamma, beta)
-        if not self.blockwise:   # the kernel's fused epilogue covers a whole head
-            for ti, oq, ov, w, kap in self._tiles():
-                self.L.call("magpo_retention_recurrent", S[ti], q[:, oq:], ldq, k[:, oq:], ldk, v[:, ov:], ldv, env_rows, u[:, ov:], ldu, N, ntok,
-                            ret_from, kap, write, gp[:, ov:], ldg, gamma, beta, w, self.gs, self._st())
-            return
+        """Acting: retention + GroupNorm / swish gate for every state tile; S [ntile, N, 64, 64].  Rows: token a of env e at e * env_rows + a;
+        written are the rows ret_from <= a < ntok of every env.  ff_sable: the same rows from the stateless team kernel (S, write unused;
+        the rows of an env are consecutive; the decoder asks for its newest token only, so the causal mask is implied by ntok)."""
+        L, E, A, st = self.L, self.E, self.A, self._st()
         R = u.shape[0]
-        raw, tmp = self.b.get("rr_raw", (R, E)), self.b.get("rr_tmp", (R, TILE))
-        for ti, oq, ov, w, kap in self._tiles():
-            first = oq == 0
-            out, ldo = (raw[:, ov:], E) if first else (tmp, TILE)
-            self.L.call("magpo_retention_recurrent", S[ti], q[:, oq:], ldq, k[:, oq:], ldk, v[:, ov:], ldv, env_rows, out, ldo, N, ntok,
-                        ret_from, kap, write, None, 0, None, None, w, w, self._st())
-            if not first:
-                self.add_rows(raw[:, ov:], E, tmp, TILE, R, TILE)   # (rows outside [ret_from, ntok) hold stale values: never read)
-        for a in range(ret_from, ntok):   # GroupNorm + swish gate on the 128-wide rows of token a of every env
-            self.L.call("magpo_retpost_fwd", raw[a:], env_rows * E, gp[a:], env_rows * ldg, gamma, beta, u[a:], env_rows * ldu, N, self.hs, self.gs,
-                        E, self._st())
-
-    # ---- ff_sable: stateless retention over teams of A consecutive rows (csrc/team_retention.hip); same tiles, no state anywhere
-    def _team_ret_act(self, q, ldq, k, ldk, v, ldv, u, ldu, N, ntok, ret_from, gp, ldg, gamma, beta):
-        """Acting: rows ret_from <= a < ntok of every env from its k / v rows a < ntok, then GroupNorm + swish gate (fused into the kernel
-        when a tile is a whole head).  The decoder asks for its newest token only, so the causal mask is implied by ntok."""
-        E, A, st = self.E, self.A, self._st()
-        masked = 0 if ret_from == 0 else 1
-        if not self.blockwise:
-            for _, oq, ov, w, _ in self._tiles():
-                self.L.call("magpo_team_retention_fwd", q[:, oq:], ldq, k[:, oq:], ldk, v[:, ov:], ldv, u[:, ov:], ldu, N, A, ntok, ret_from, masked, w,
-                            gp[:, ov:], ldg, gamma, beta, self.gs, st)
-            return
-        R = u.shape[0]
-        raw, tmp = self.b.get("rr_raw", (R, E)), self.b.get("rr_tmp", (R, TILE))
-        for _, oq, ov, w, _ in self._tiles():
-            first = oq == 0
-            out, ldo = (raw[:, ov:], E) if first else (tmp, TILE)
-            self.L.call("magpo_team_retention_fwd", q[:, oq:], ldq, k[:, oq:], ldk, v[:, ov:], ldv, out, ldo, N, A, ntok, ret_from, masked, w,
-                        None, 0, None, None, 0, st)
-            if not first:
-                self.add_rows(raw[:, ov:], E, tmp, TILE, R, TILE)   # (rows outside [ret_from, ntok) hold stale values: never read)
-        for a in range(ret_from, ntok):
-            self.L.call("magpo_retpost_fwd", raw[a:], A * E, gp[a:], A * ldg, gamma, beta, u[a:], A * ldu, N, self.hs, self.gs, E, st)
-
-    def _team_ret_fwd(self, q, ldq, k, ldk, v, ldv, r, nteams, masked):
-        E, R = self.E, nteams * self.A
-        for _, oq, ov, w, _ in self._tiles():
-            partial = self.blockwise and oq != 0
-            out, ldo = (self.b.get("rf_tmp", (R, TILE)), TILE) if partial else (r[:, ov:], E)
-            self.L.call("magpo_team_retention_fwd", q[:, oq:], ldq, k[:, oq:], ldk, v[:, ov:], ldv, out, ldo, nteams, self.A, self.A, 0, masked, w,
-                        None, 0, None, None, 0, self._st())
-            if partial:
-                self.add_rows(r[:, ov:], E, out, TILE, R, TILE)
-
-    def _team_ret_bwd(self, q, ldq, k, ldk, v, ldv, dr, dq, lddq, dk, lddk, dv, lddv, nteams, masked):
-        E, R = self.E, nteams * self.A
-        for _, oq, ov, w, _ in self._tiles():
-            if not self.blockwise:
-                self.L.call("magpo_team_retention_bwd", q[:, oq:], ldq, k[:, oq:], ldk, v[:, ov:], ldv, dr[:, ov:], E, dq[:, oq:], lddq, dk[:, oq:],
-                            lddk, dv[:, ov:], lddv, nteams, self.A, masked, w, self._st())
-                continue
-            # block (I, J) of the 128-wide head: dq_I, dk_I add over J; dv_J adds over I
-            tq, tk, tv = (self.b.get(f"rb_t{c}", (R, TILE)) for c in "qkv")
-            qk_first, v_first = ov == 0, oq == 0
-            oq_, ldq_ = (dq[:, oq:], lddq) if qk_first else (tq, TILE)
-            ok_, ldk_ = (dk[:, oq:], lddk) if qk_first else (tk, TILE)
-            ov_, ldv_ = (dv[:, ov:], lddv) if v_first else (tv, TILE)
-            self.L.call("magpo_team_retention_bwd", q[:, oq:], ldq, k[:, oq:], ldk, v[:, ov:], ldv, dr[:, ov:], E, oq_, ldq_, ok_, ldk_, ov_, ldv_,
-                        nteams, self.A, masked, w, self._st())
-            if not qk_first:
-                self.add_rows(dq[:, oq:], lddq, tq, TILE, R, TILE)
-                self.add_rows(dk[:, oq:], lddk, tk, TILE, R, TILE)
-            if not v_first:
-                self.add_rows(dv[:, ov:], lddv, tv, TILE, R, TILE)
+        if self.ff:   # (``post`` / ``gs``: the fused GroupNorm + gate epilogue and its group size; none and 0 for a block of the 128-wide head)
+            assert env_rows == A
+            masked = 0 if ret_from == 0 else 1
+            launch = lambda ti, kap, w, qkv, post, gs, out, ldo: L.call("magpo_team_retention_fwd", *qkv, out, ldo, N, A, ntok, ret_from, masked, w,
+                                                                        *post, gs, st)
+        else:
+            launch = lambda ti, kap, w, qkv, post, gs, out, ldo: L.call("magpo_retention_recurrent", S[ti], *qkv, env_rows, out, ldo, N, ntok, ret_from,
+                                                                        kap, write, *post, w, gs or w, st)
+        raw = self.b.get("rr_raw", (R, E)) if self.blockwise else None
+        for ti, oq, ov, w, kap, first_v, _ in self._tiles():
+            qkv = (q[:, oq:], ldq, k[:, oq:], ldk, v[:, ov:], ldv)
+            if raw is None:   # the kernel's fused epilogue covers a whole head
+                launch(ti, kap, w, qkv, (gp[:, ov:], ldg, gamma, beta), self.gs, u[:, ov:], ldu)
+            else:             # (rows outside [ret_from, ntok) hold stale values: never read)
+                self._tile_launch(partial(launch, ti, kap, w, qkv, (None, 0, None, None), 0), R, (raw[:, ov:], E, first_v, "rr_tmp"))
+        if raw is not None:
+            for a in range(ret_from, ntok):   # GroupNorm + swish gate on the 128-wide rows of token a of every env
+                L.call("magpo_retpost_fwd", raw[a:], env_rows * E, gp[a:], env_rows * ldg, gamma, beta, u[a:], env_rows * ldu, N, self.hs, self.gs, E, st)
 
     def _ret_fwd(self, q, ldq, k, ldk, v, ldv, r, s0, seq_env, dones, name, nseq, T, masked, rows=None):
-        """``rows`` (i32 [R], optional): q | k | v are row tables and token row r reads table row rows[r] (csrc/classtab.hip)."""
-        if self.ff:   # no t_* state buffers, no s0, no dones
-            assert T == 1 and rows is None
-            return self._team_ret_fwd(q, ldq, k, ldk, v, ldv, r, nseq, masked)
-        ct = self.tuning.ret_chunk_tokens
-        nch = self.L.call("magpo_retention_num_chunks", T, self.A, ct)
-        E, R = self.E, nseq * T * self.A
-        for ti, oq, ov, w, kap in self._tiles():
-            stt = self.b.get(f"t_{name}_{ti}", (nseq, nch, TILE, TILE))
-            partial = self.blockwise and oq != 0   # second q / k half of the 128-wide head: its contribution adds to the first one's
-            out, ldo = (self.b.get("rf_tmp", (R, TILE)), TILE) if partial else (r[:, ov:], E)
-            self.L.call("magpo_retention_chunk_fwd", q[:, oq:], ldq, k[:, oq:], ldk, v[:, ov:], ldv, out, ldo, s0[ti], seq_env, dones, stt,
-                        None, nseq, T, self.A, masked, kap, w, rows, ct, self._st())
-            if partial:
-                self.add_rows(r[:, ov:], E, out, TILE, R, TILE)
-
-    def _ret_bwd(self, q, ldq, k, ldk, v, ldv, dr, dq, lddq, dk, lddk, dv, lddv, dones, name, nseq, T, masked, rows=None):
+        """Training forward: r [R, E] for every state tile; keeps the chunk states ``t_{name}_{tile}`` for the backward.  ``rows`` (i32 [R],
+        optional): q | k | v are row tables and token row r reads table row rows[r] (csrc/classtab.hip).  ff_sable: stateless retention
+        over teams of A consecutive rows (csrc/team_retention.hip) -- no t_* state buffers, no s0, no dones."""
+        L, b, E, A, st = self.L, self.b, self.E, self.A, self._st()
         if self.ff:
             assert T == 1 and rows is None
-            return self._team_ret_bwd(q, ldq, k, ldk, v, ldv, dr, dq, lddq, dk, lddk, dv, lddv, nseq, masked)
-        ct = self.tuning.ret_chunk_tokens
-        E, R = self.E, nseq * T * self.A
-        for ti, oq, ov, w, kap in self._tiles():
-            stt = self.b.t[f"t_{name}_{ti}"]
-            if not self.blockwise:
-                self.L.call("magpo_retention_chunk_bwd", q[:, oq:], ldq, k[:, oq:], ldk, v[:, ov:], ldv, dr[:, ov:], E, dq[:, oq:], lddq, dk[:, oq:],
-                            lddk, dv[:, ov:], lddv, dones, stt, nseq, T, self.A, masked, kap, w, rows, ct, self._st())
-                continue
+            launch = lambda ti, kap, w, qkv, out, ldo: L.call("magpo_team_retention_fwd", *qkv, out, ldo, nseq, A, A, 0, masked, w, None, 0, None, None, 0, st)
+        else:
+            ct = self.tuning.ret_chunk_tokens
+            nch = L.call("magpo_retention_num_chunks", T, A, ct)
+            launch = lambda ti, kap, w, qkv, out, ldo: L.call("magpo_retention_chunk_fwd", *qkv, out, ldo, s0[ti], seq_env, dones,
+                                                              b.get(f"t_{name}_{ti}", (nseq, nch, TILE, TILE)), None, nseq, T, A, masked, kap, w, rows, ct, st)
+        for ti, oq, ov, w, kap, first_v, _ in self._tiles():
+            qkv = (q[:, oq:], ldq, k[:, oq:], ldk, v[:, ov:], ldv)
+            self._tile_launch(partial(launch, ti, kap, w, qkv), nseq * T * A, (r[:, ov:], E, first_v, "rf_tmp"))
+
+    def _ret_bwd(self, q, ldq, k, ldk, v, ldv, dr, dq, lddq, dk, lddk, dv, lddv, dones, name, nseq, T, masked, rows=None):
+        """Training backward of :meth:`_ret_fwd`: dq, dk, dv from dr [R, E]."""
+        L, b, E, A, st = self.L, self.b, self.E, self.A, self._st()
+        if self.ff:
+            assert T == 1 and rows is None
+            launch = lambda ti, kap, w, io, *d: L.call("magpo_team_retention_bwd", *io, *d, nseq, A, masked, w, st)
+        else:
+            ct = self.tuning.ret_chunk_tokens
+            launch = lambda ti, kap, w, io, *d: L.call("magpo_retention_chunk_bwd", *io, *d, dones, b.t[f"t_{name}_{ti}"], nseq, T, A, masked, kap, w,
+                                                       rows, ct, st)
+        for ti, oq, ov, w, kap, first_v, first_qk in self._tiles():
+            io = (q[:, oq:], ldq, k[:, oq:], ldk, v[:, ov:], ldv, dr[:, ov:], E)
             # block (I, J) of the 128-wide head: dq_I, dk_I add over J; dv_J adds over I
-            tq, tk, tv = (self.b.get(f"rb_t{c}", (R, TILE)) for c in "qkv")
-            qk_first, v_first = ov == 0, oq == 0
-            oq_, ldq_ = (dq[:, oq:], lddq) if qk_first else (tq, TILE)
-            ok_, ldk_ = (dk[:, oq:], lddk) if qk_first else (tk, TILE)
-            ov_, ldv_ = (dv[:, ov:], lddv) if v_first else (tv, TILE)
-            self.L.call("magpo_retention_chunk_bwd", q[:, oq:], ldq, k[:, oq:], ldk, v[:, ov:], ldv, dr[:, ov:], E, oq_, ldq_, ok_, ldk_,
-                        ov_, ldv_, dones, stt, nseq, T, self.A, masked, kap, w, rows, ct, self._st())
-            if not qk_first:
-                self.add_rows(dq[:, oq:], lddq, tq, TILE, R, TILE)
-                self.add_rows(dk[:, oq:], lddk, tk, TILE, R, TILE)
-            if not v_first:
-                self.add_rows(dv[:, ov:], lddv, tv, TILE, R, TILE)
+            self._tile_launch(partial(launch, ti, kap, w, io), nseq * T * A, (dq[:, oq:], lddq, first_qk, "rb_tq"), (dk[:, oq:], lddk, first_qk, "rb_tk"),
+                              (dv[:, ov:], lddv, first_v, "rb_tv"))
 
     def act(self, obs, pos, states, sample_keys, action_out, logp_out, value_out, mask=None, value_only=False):
         """One env step for N envs (SableNetwork.get_actions, sable_network.py:443-482).  obs [N,A,F] f32, pos [N] i32
@@ -421,6 +360,7 @@ class SableGuider(NetBase):
         q2 = [b.get(f"d_q2_{k}", (R, E)) for k in range(nb)]
         kvg2 = [b.get(f"d_kvg2_{k}", (R, 3 * E)) for k in range(nb)]
         u1 = b.get("d_u1", (R, E)); u2 = b.get("d_u2", (R, E))
+        keys, kdev = self._sample_keys_arg(sample_keys)
         for blk in range(nb):   # cross-retention queries of all agents at once
             self.lin(reppe, E, self.wt[f"q2{blk}"], None, q2[blk], E, R, E, E)
         for i in range(A):
@@ -450,12 +390,33 @@ class SableGuider(NetBase):
                            xo, E, xope, E, N, E, st)
             self._pro(4, hp, E, None, 0, v["dec.head.norm.scale"], None, False, pos, 1, None, None, 0, None, 0, None, 0,
                       self.wt["h1"], v["dec.head.dense1.bias"], logits, LW, N, K)
-            if torch.is_tensor(sample_keys):   # device key table [A, 2] (static arguments: HIP-graph replay)
-                k0, k1, kdev = 0, 0, sample_keys[i]
-            else:
-                k0, k1, kdev = int(sample_keys[i][0]), int(sample_keys[i][1]), None
+            k0, k1 = (0, 0) if keys is None else (int(keys[i][0]), int(keys[i][1]))
             L.call("magpo_sample_categorical", logits, LW, None if mask is None else mask[:, i], (A * K if mask is not None else 0),
-                   k0, k1, kdev, action_out[:, i:], A, logp_out[:, i:], A, prev[:, i + 1:] if i + 1 < A else None, A, None, 0, N, K, st)
+                   k0, k1, None if kdev is None else kdev[i], action_out[:, i:], A, logp_out[:, i:], A, prev[:, i + 1:] if i + 1 < A else None, A, None, 0, N, K, st)
+
+    def _sample_keys_arg(self, sample_keys, value_only=False):
+        """``sample_keys`` [A, 2] uint32 as (host array or None, device table or None): a device tensor goes to the kernels as it is (static
+        arguments for HIP-graph replay), host keys go by value; ``value_only`` samples nothing and needs none."""
+        if torch.is_tensor(sample_keys):
+            return None, sample_keys
+        if value_only:
+            return None, None
+        return np.ascontiguousarray(np.asarray(sample_keys, dtype=np.uint32).reshape(self.A, 2)), None
+
+    def _head_params(self, w):
+        """The 15 embedding / head entries the one-launch acting kernels' tables share, in the order of include/magpo.h; ``w``: the weight
+        copies the kernel reads (``wa`` fragment-major, ``wt`` transposed)."""
+        v = self.v
+        return [v["enc.obs.norm.scale"], v["enc.obs.dense.kernel"], v["enc.ln.scale"], v["dec.act.kernel"], v["dec.ln.scale"],
+                w["vh0"], v["enc.head.dense0.bias"], v["enc.head.norm.scale"], v["enc.head.dense1.kernel"], v["enc.head.dense1.bias"],
+                w["h0"], v["dec.head.dense0.bias"], v["dec.head.norm.scale"], w["h1"], v["dec.head.dense1.bias"]]
+
+    def _block_params(self, k, w):
+        """The 18 per-block entries of the same tables for block ``k``, in header order."""
+        v, e, d = self.v, f"enc.block{k}.", f"dec.block{k}."
+        return [w[f"qkvg{k}"], w[f"wo{k}"], v[e + "ln1.scale"], v[e + "ln2.scale"], v[e + "retn.gn.scale"], v[e + "retn.gn.bias"],
+                w[f"qkvg1{k}"], w[f"wo1{k}"], v[d + "ln1.scale"], v[d + "retn1.gn.scale"], v[d + "retn1.gn.bias"],
+                w[f"q2{k}"], w[f"kvg2{k}"], w[f"wo2{k}"], v[d + "ln2.scale"], v[d + "ln3.scale"], v[d + "retn2.gn.scale"], v[d + "retn2.gn.bias"]]
 
     def act_fused(self, obs, pos, states, sample_keys, action_out, logp_out, value_out, mask=None, value_only=False, done=None, tag="",
                   pending=False, flush=True, precand=False, defer=False):
@@ -481,18 +442,14 @@ class SableGuider(NetBase):
             return self.act(obs, pos, states, sample_keys, action_out, logp_out, value_out, mask=mask, value_only=value_only)
         N = obs.shape[0]
         R = N * A
-        v, b = self.v, self.b
+        b = self.b
         s_enc, s_d1, s_d2 = states   # value_only (bootstrap value, rec_magpo.py:202-208): the kernel writes no state
-        kdev = sample_keys if torch.is_tensor(sample_keys) else None
+        keys, kdev = self._sample_keys_arg(sample_keys, value_only)
         args = (obs, pos, mask, kdev, s_enc, s_d1, s_d2, action_out, logp_out, value_out, done)
 
         def table():   # the global pointers, then 21 per block (everything beside ``args``: parameters, weight copies, scratch of (tag, N))
-            wa = self.wa
             g = lambda n, w=E, rows=R: b.get(f"f{tag}_" + n, (rows, w))   # scratch per caller tag (env groups may act concurrently)
-            glob = [obs, pos, mask, kdev,
-                    v["enc.obs.norm.scale"], v["enc.obs.dense.kernel"], v["enc.ln.scale"], v["dec.act.kernel"], v["dec.ln.scale"],
-                    wa["vh0"], v["enc.head.dense0.bias"], v["enc.head.norm.scale"], v["enc.head.dense1.kernel"], v["enc.head.dense1.bias"],
-                    wa["h0"], v["dec.head.dense0.bias"], v["dec.head.norm.scale"], wa["h1"], v["dec.head.dense1.bias"],
+            glob = [obs, pos, mask, kdev, *self._head_params(self.wa),
                     self.pe, s_enc, s_d1, s_d2,
                     g("xn"), done, g("qkvg", 4 * E), g("u"), g("y"), g("rep"), g("reppe"), g("hv"),
                     g("xa", E, N), g("kin1", E, N), g("y1", E, N), g("c", E, N), g("cpe", E, N), g("y2", E, N), g("xo", E, N),
@@ -501,12 +458,7 @@ class SableGuider(NetBase):
                     b.get(f"f{tag}_ptab", (N, (K + 2) * E)) if nh == 1 else None]
             blk = []
             for k in range(nb):
-                e, d = f"enc.block{k}.", f"dec.block{k}."
-                blk += [wa[f"qkvg{k}"], wa[f"wo{k}"], v[e + "ln1.scale"], v[e + "ln2.scale"], v[e + "retn.gn.scale"], v[e + "retn.gn.bias"],
-                        wa[f"qkvg1{k}"], wa[f"wo1{k}"], v[d + "ln1.scale"], v[d + "retn1.gn.scale"], v[d + "retn1.gn.bias"],
-                        wa[f"q2{k}"], wa[f"kvg2{k}"], wa[f"wo2{k}"], v[d + "ln2.scale"], v[d + "ln3.scale"],
-                        v[d + "retn2.gn.scale"], v[d + "retn2.gn.bias"],
-                        g(f"qkvg1_{k}", 4 * E), g(f"q2_{k}"), g(f"kvg2_{k}", 4 * E)]   # kvg2 rows: [k | v | - | P2] (ld 256)
+                blk += self._block_params(k, self.wa) + [g(f"qkvg1_{k}", 4 * E), g(f"q2_{k}"), g(f"kvg2_{k}", 4 * E)]   # kvg2 rows: [k | v | - | P2] (ld 256)
             return glob + blk
 
         tab = self.ptr_table(("act", tag, N) + tuple(None if t is None else t.data_ptr() for t in args), table)
@@ -514,9 +466,6 @@ class SableGuider(NetBase):
         dims = np.array([N, A, K, F, nb, nh, self.hs, self.gs, self.npos, 1 if value_only else 0, self.Fld, self.tuning.act_envs_per_wave,
                          1 if pending else 0, 1 if flush else 0, 1 if precand else 0, 1 if defer else 0], dtype=np.int32)
         kap = np.array((self.kappas + [0.0] * 4)[:4], dtype=np.float32)
-        keys = None
-        if kdev is None and not value_only:
-            keys = np.ascontiguousarray(np.asarray(sample_keys, dtype=np.uint32).reshape(A, 2))
         self.L.call("magpo_sable_act", dims.ctypes.data, kap.ctypes.data, None if keys is None else keys.ctypes.data,
                     gp.ctypes.data, int(gp.size), bp.ctypes.data, int(bp.size), self._st())
 
@@ -534,32 +483,19 @@ class SableGuider(NetBase):
                              "through act_fused")
         if not self.team_fused_supported():
             return self.act(obs, pos, states, sample_keys, action_out, logp_out, value_out, mask=mask, value_only=value_only)
-        A, K, nb, v, wt = self.A, self.K, self.nb, self.v, self.wt
+        A, K, nb = self.A, self.K, self.nb
         N = obs.shape[0]
-        kdev = sample_keys if torch.is_tensor(sample_keys) else None
+        keys, kdev = self._sample_keys_arg(sample_keys, value_only)
         need = 32 * ((N + 31) // 32) * A * (384 + 256 * nb)
         args = (obs, mask, kdev, action_out, logp_out, value_out)
 
         def table():   # 22 global pointers, then 18 per block (include/magpo.h)
-            glob = [obs, mask, kdev, v["enc.obs.norm.scale"], v["enc.obs.dense.kernel"], v["enc.ln.scale"], v["dec.act.kernel"], v["dec.ln.scale"],
-                    wt["vh0"], v["enc.head.dense0.bias"], v["enc.head.norm.scale"], v["enc.head.dense1.kernel"], v["enc.head.dense1.bias"],
-                    wt["h0"], v["dec.head.dense0.bias"], v["dec.head.norm.scale"], wt["h1"], v["dec.head.dense1.bias"],
-                    self.b.get(f"tf_scratch{need}", (need,)), action_out, logp_out, value_out]
-            blk = []
-            for k in range(nb):
-                e, d = f"enc.block{k}.", f"dec.block{k}."
-                blk += [wt[f"qkvg{k}"], wt[f"wo{k}"], v[e + "ln1.scale"], v[e + "ln2.scale"], v[e + "retn.gn.scale"], v[e + "retn.gn.bias"],
-                        wt[f"qkvg1{k}"], wt[f"wo1{k}"], v[d + "ln1.scale"], v[d + "retn1.gn.scale"], v[d + "retn1.gn.bias"],
-                        wt[f"q2{k}"], wt[f"kvg2{k}"], wt[f"wo2{k}"], v[d + "ln2.scale"], v[d + "ln3.scale"],
-                        v[d + "retn2.gn.scale"], v[d + "retn2.gn.bias"]]
-            return glob + blk
+            glob = [obs, mask, kdev, *self._head_params(self.wt), self.b.get(f"tf_scratch{need}", (need,)), action_out, logp_out, value_out]
+            return glob + [t for k in range(nb) for t in self._block_params(k, self.wt)]
 
         tab = self.ptr_table(("act_team", N) + tuple(None if t is None else t.data_ptr() for t in args), table)
         gp, bp = tab[:22], tab[22:]
         dims = np.array([N, A, K, self.F, nb, self.nh, self.hs, self.gs, 1 if value_only else 0, self.Fld], dtype=np.int32)
-        keys = None
-        if kdev is None and not value_only:
-            keys = np.ascontiguousarray(np.asarray(sample_keys, dtype=np.uint32).reshape(A, 2))
         self.L.call("magpo_ff_sable_act", dims.ctypes.data, None if keys is None else keys.ctypes.data, gp.ctypes.data, int(gp.size),
                     bp.ctypes.data, int(bp.size), need, self._st())
 
@@ -640,6 +576,39 @@ class SableGuider(NetBase):
             self.reduce(sa[:, h * self.hs:], gv[pfx + "gn.scale"], P=self.hs, stride=E, accumulate=h > 0)
             self.reduce(sb[:, h * self.hs:], gv[pfx + "gn.bias"], P=self.hs, stride=E, accumulate=h > 0)
 
+    def _class_fwd(self, side):
+        """Block 0 of ``side`` ("enc" / "dec") on its class table: the embedding and the first q|k|v|g projection on the C distinct input
+        rows; unless the block's consumers read the tables through the class index (``direct``), both are gathered by class into the
+        per-token buffers.  Returns (block input [C, E], q|k|v|g [C, 4E]); ``_class_bwd`` is the backward."""
+        L, st, b, v, E, F, sv = self.L, self._st(), self.b, self.v, self.E, self.F, self._saved
+        rows = sv["classes"]["rows"]
+        if side == "enc":   # observation embedding: names of x, x + pe and the projection (= its weight copy's)
+            (inp, pos_c), (x, xpe, proj) = rows[:2], ("xn0", "kin0", "qkvg0")
+            embed = (0, inp, F, F, v["enc.obs.norm.scale"], v["enc.obs.dense.kernel"], None, 0, v["enc.ln.scale"])
+        else:               # action embedding
+            (inp, pos_c), (x, xpe, proj) = rows[2:], ("x0", "xpe0", "qkvg10")
+            embed = (1, None, 0, 0, None, v["dec.act.kernel"], inp, 1, v["dec.ln.scale"])
+        C, R = inp.shape[0], sv["R"]
+        x_c, xpe_c, qkvg_c = b.get("c_" + x, (C, E)), b.get("c_" + xpe, (C, E)), b.get("c_" + proj, (C, 4 * E))
+        L.call("magpo_embed_fwd", *embed, self.pe, pos_c, 1, self.npos, None, 0, x_c, E, xpe_c, E, C, E, st)
+        self.lin(xpe_c, E, self.wt[proj], None, qkvg_c, 4 * E, C, E, 4 * E)
+        if not sv["direct"]:   # per-token copies for the unfused segment kernels; the fused ones read the tables through the class index
+            cls = sv["classes"][side][0]
+            L.call("magpo_gather_rows", x_c, E, cls, b.get("t_" + x, (R, E)), E, R, E, st)
+            L.call("magpo_gather_rows", qkvg_c, 4 * E, cls, b.get("t_" + proj, (R, 4 * E)), 4 * E, R, 4 * E, st)
+        return x_c, qkvg_c
+
+    def _obs_embed_bwd(self, d0, d1, obs, ldo, R, grid, sfx, accumulate):
+        """Backward of the observation embedding on R rows of ``obs`` (stride ldo) from the gradient d0 + d1 at its output, with the three
+        parameter gradients from the slabs ``s_{a,w,d}{sfx}`` of ``grid`` rows (enc.ln.scale: shared by the blocks, hence ``accumulate``)."""
+        b, v, gv, E, F = self.b, self.v, self.gv, self.E, self.F
+        sa, sw, sd = b.get("s_a" + sfx, (grid, E)), b.get("s_w" + sfx, (grid, 32 * E)), b.get("s_d" + sfx, (grid, 32))
+        self.L.call("magpo_embed_bwd", 0, None, 0, d0, E, d1, E, None, 0, v["enc.ln.scale"], None, 0, sa, sw, F,
+                    obs, ldo, F, v["enc.obs.norm.scale"], v["enc.obs.dense.kernel"], sd, None, 0, R, E, self._st())
+        self.reduce(sa, gv["enc.ln.scale"], accumulate=accumulate)
+        self.reduce(sd, gv["enc.obs.norm.scale"], P=F, stride=32)
+        self.reduce(sw, gv["enc.obs.dense.kernel"], P=F * E, stride=32 * E)
+
     def _class_bwd(self, side, dqkvg, dsum, kin_c, wname):
         """Block 0 of ``side`` ("enc" / "dec") on its class table: the per-class sums of both gradient paths into the block input, then on
         the C class rows the weight gradient of the q|k|v|g projection ``wname`` (input rows ``kin_c``) and its dX.
@@ -677,15 +646,7 @@ class SableGuider(NetBase):
         logits = b.get("t_logits", (R, LW), zero=True)
         # ---- encoder
         if classes is not None:   # embedding + first projection on the Ce distinct (agent, target, step) rows, gathered by class
-            obs_c, pos_c = classes["rows"][0], classes["rows"][1]
-            Ce = obs_c.shape[0]
-            xn_c, kin_c, qkvg_c = b.get("c_xn0", (Ce, E)), b.get("c_kin0", (Ce, E)), b.get("c_qkvg0", (Ce, 4 * E))
-            L.call("magpo_embed_fwd", 0, obs_c, F, F, v["enc.obs.norm.scale"], v["enc.obs.dense.kernel"], None, 0, v["enc.ln.scale"],
-                   self.pe, pos_c, 1, self.npos, None, 0, xn_c, E, kin_c, E, Ce, E, st)
-            self.lin(kin_c, E, self.wt["qkvg0"], None, qkvg_c, 4 * E, Ce, E, 4 * E)
-            if not direct:   # per-token copies for the unfused segment kernels; the fused ones read the tables through the class index
-                L.call("magpo_gather_rows", xn_c, E, classes["enc"][0], g("xn0"), E, R, E, st)
-                L.call("magpo_gather_rows", qkvg_c, 4 * E, classes["enc"][0], g("qkvg0", 4 * E), 4 * E, R, 4 * E, st)
+            xn_c, qkvg_c = self._class_fwd("enc")
         elif self.wide:   # obs_encoder + ln on padded rows: RMSNorm_F -> Dense on the MFMA kernel -> GELU + RMSNorm (sable_network.py:93-101,132)
             on, z0 = b.get("t_on", (R, 128)), g("z0")
             L.call("magpo_obsnorm_fwd", obs, self.Fld, F, v["enc.obs.norm.scale"], on, R, st)
@@ -719,15 +680,7 @@ class SableGuider(NetBase):
                        g(f"xn{k + 1}"), E, g(f"kin{k + 1}"), E, R, E, st)
         # ---- decoder
         if classes is not None:   # action embedding + first projection on the Cd distinct (previous action, step) rows
-            prev_c, posd_c = classes["rows"][2], classes["rows"][3]
-            Cd = prev_c.shape[0]
-            x_c, xpe_c, qkvg1_c = b.get("c_x0", (Cd, E)), b.get("c_xpe0", (Cd, E)), b.get("c_qkvg10", (Cd, 4 * E))
-            L.call("magpo_embed_fwd", 1, None, 0, 0, None, v["dec.act.kernel"], prev_c, 1, v["dec.ln.scale"], self.pe, posd_c, 1, self.npos,
-                   None, 0, x_c, E, xpe_c, E, Cd, E, st)
-            self.lin(xpe_c, E, self.wt["qkvg10"], None, qkvg1_c, 4 * E, Cd, E, 4 * E)
-            if not direct:
-                L.call("magpo_gather_rows", x_c, E, classes["dec"][0], g("x0"), E, R, E, st)
-                L.call("magpo_gather_rows", qkvg1_c, 4 * E, classes["dec"][0], g("qkvg10", 4 * E), 4 * E, R, 4 * E, st)
+            x_c, qkvg1_c = self._class_fwd("dec")
         else:
             L.call("magpo_embed_fwd", 1, None, 0, 0, None, v["dec.act.kernel"], prev_idx, 1, v["dec.ln.scale"], self.pe, pos, 1, self.npos,
                    None, 0, g("x0"), E, g("xpe0"), E, R, E, st)   # za = W_act[prev] is gathered again by the backward
@@ -850,14 +803,7 @@ class SableGuider(NetBase):
                           dones, f"st_e{k}", nseq, T, 0, rows=rows)
             if k == 0 and cl is not None:
                 ds_c, dkin, Ce = self._class_bwd("enc", dqkvg, dsum0, b.t["c_kin0"], e + "retn.w_qkvg")
-                obs_c = cl["rows"][0]
-                gride = L.call("magpo_row_grid", Ce)
-                sa, sw, sd = b.get("s_a_e", (gride, E)), b.get("s_w_e", (gride, 32 * E)), b.get("s_d_e", (gride, 32))
-                L.call("magpo_embed_bwd", 0, None, 0, ds_c, E, dkin, E, None, 0, v["enc.ln.scale"], None, 0, sa, sw, F,
-                       obs_c, F, F, v["enc.obs.norm.scale"], v["enc.obs.dense.kernel"], sd, None, 0, Ce, E, st)
-                self.reduce(sa, gv["enc.ln.scale"], accumulate=not first_ln)
-                self.reduce(sd, gv["enc.obs.norm.scale"], P=F, stride=32)
-                self.reduce(sw, gv["enc.obs.dense.kernel"], P=F * E, stride=32 * E)
+                self._obs_embed_bwd(ds_c, dkin, cl["rows"][0], F, Ce, L.call("magpo_row_grid", Ce), "_e", not first_ln)
                 break
             self.wgrad(t(f"kin{k}"), E, dqkvg, 4 * E, R, E, 4 * E, gv[e + "retn.w_qkvg"])
             dkin = g(f"dkin_{k}")
@@ -881,11 +827,7 @@ class SableGuider(NetBase):
                 L.call("magpo_obsnorm_bwd", obs, self.Fld, F, don, so, R, st)
                 self.reduce(so, gv["enc.obs.norm.scale"], P=F, stride=128)
             else:
-                L.call("magpo_embed_bwd", 0, None, 0, dsum0, E, dkin, E, None, 0, v["enc.ln.scale"], None, 0, slab("a"), slab("w", 32 * E), F,
-                       obs, self.Fld, F, v["enc.obs.norm.scale"], v["enc.obs.dense.kernel"], slab("d", 32), None, 0, R, E, st)
-                self.reduce(slab("a"), gv["enc.ln.scale"], accumulate=not first_ln)
-                self.reduce(slab("d", 32), gv["enc.obs.norm.scale"], P=F, stride=32)
-                self.reduce(slab("w", 32 * E), gv["enc.obs.dense.kernel"], P=F * E, stride=32 * E)
+                self._obs_embed_bwd(dsum0, dkin, obs, self.Fld, R, grid, "", not first_ln)
         self._join_wgrad()
         if self.emb is not None:   # gradient of a logical parameter = sum over its tied device copies
             self.emb.fold(self.grads_D, self.grads)

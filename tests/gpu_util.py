@@ -94,3 +94,17 @@ def reduce_slabs(L, st, slab, G, P, stride, out=None):
     out = torch.empty(P, device=DEV) if out is None else out
     L.call("magpo_reduce_slabs", slab, out, G, P, stride, 1.0, 0, st)
     return out
+
+
+def _count_calls(L, counts, fn):
+    """Run fn() with every ABI call counted by name."""
+    orig = L.call
+
+    def counting(name, *a):
+        counts[name] = counts.get(name, 0) + 1
+        return orig(name, *a)
+    L.call = counting
+    try:
+        return fn()
+    finally:
+        del L.call

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from tests import kernel_refs as kr
-from tests.gpu_util import DEV, Guard
+from tests.gpu_util import DEV, Guard, _count_calls
 
 pytestmark = pytest.mark.gpu
 
@@ -149,20 +149,6 @@ def test_same_values_as_the_pair(L, stream, KIN, NOUT, R):
         for n in ("dX", "dW", "db"):
             d = (new[n].out != old[n])
             assert not bool(d.any()), f"{KIN}x{NOUT} R={R} G={G} {mode}: {n} differs from the pair in {int(d.sum())} elements"
-
-
-def _count_calls(L, counts, fn):
-    """Run fn() with every ABI call counted by name (as tests/test_ff_sable_learner_gpu.py does)."""
-    orig = L.call
-
-    def counting(name, *a):
-        counts[name] = counts.get(name, 0) + 1
-        return orig(name, *a)
-    L.call = counting
-    try:
-        return fn()
-    finally:
-        del L.call
 
 
 def close(a, b, rtol, atol, what):

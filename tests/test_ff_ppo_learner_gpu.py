@@ -14,6 +14,7 @@ import torch
 
 from oracle import prng as oprng
 from tests import ff_ppo_ref as fr
+from tests.gpu_util import _count_calls
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -92,20 +93,6 @@ def _sync_oracle(ol, dl):
             p[n] = net.named[n].detach().cpu().reshape(p[n].shape).clone()
             o["mu"][n] = mn[n].detach().cpu().reshape(p[n].shape).clone()
             o["nu"][n] = nn[n].detach().cpu().reshape(p[n].shape).clone()
-
-
-def _count_calls(L, counts, fn):
-    """Run fn() with every ABI call counted by name."""
-    orig = L.call
-
-    def counting(name, *a):
-        counts[name] = counts.get(name, 0) + 1
-        return orig(name, *a)
-    L.call = counting
-    try:
-        return fn()
-    finally:
-        del L.call
 
 
 def _three_steps(case, steps=(1, 2, 3)):

@@ -16,25 +16,11 @@ import pytest
 import torch
 
 from tests import ff_sable_act_cases as fc
-from tests.gpu_util import DEV, Guard, ptr_table
+from tests.gpu_util import DEV, Guard, _count_calls, ptr_table
 
 pytestmark = pytest.mark.gpu
 U24 = 2.0 ** -24
 HUGE = 3.0e38
-
-
-def _count_calls(L, counts, fn):
-    """Run fn() with every ABI call counted by name."""
-    orig = L.call
-
-    def counting(name, *a):
-        counts[name] = counts.get(name, 0) + 1
-        return orig(name, *a)
-    L.call = counting
-    try:
-        return fn()
-    finally:
-        del L.call
 
 
 def _guider(cid, memory_type="ff_sable"):

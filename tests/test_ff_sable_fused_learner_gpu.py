@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.gpu_util import _count_calls
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 T = 8
@@ -15,20 +17,6 @@ def close(a, b, rtol, atol, what):
     a, b = a.detach().cpu().double().reshape(-1), b.detach().cpu().double().reshape(-1)
     err, ref = (a - b).abs().max().item(), b.abs().max().item()
     assert err <= atol + rtol * ref, f"{what}: max err {err:.3e} (ref scale {ref:.3e})"
-
-
-def _count_calls(L, counts, fn):
-    """Run fn() with every ABI call counted by name."""
-    orig = L.call
-
-    def counting(name, *a):
-        counts[name] = counts.get(name, 0) + 1
-        return orig(name, *a)
-    L.call = counting
-    try:
-        return fn()
-    finally:
-        del L.call
 
 
 def _learner(fused, env_cfg=None, N=8, seed=4, num_groups=1, use_graph=False, P=1, M=1):

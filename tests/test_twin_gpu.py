@@ -78,3 +78,78 @@ def test_twin_has_the_layout_and_settings_and_acts_bit_equal_on_loaded_parameter
     for a, b in zip(got, want):
         assert a.data_ptr() != b.data_ptr() and torch.equal(a, b) and bool(torch.isfinite(b.float()).all())
     assert all(bool(t.any()) for t in want[1:] or want)     # (a sampled action table may be all zero; what is behind it is not)
+
+
+# ---------------------------------------------------------------------------------------------------------------- bind_grads
+BA, BK, BF, BNSEQ, BT = 2, 3, 5, 2, 2     # the smallest shape every training forward accepts: 2 sequences x 2 steps x 2 agents
+
+
+def _bind_case(kind):
+    """(net, run): ``run()`` is one training forward / backward on fixed inputs, which fills ``net.grads``."""
+    from magpo_amd.actor import GruActor
+    from magpo_amd.critic import GruCritic
+    from magpo_amd.ff_nets import FfActor
+    from magpo_amd.qmix_net import QMixer
+    from magpo_amd.sable import SableGuider
+    from magpo_amd.tuning import Tuning
+    g = torch.Generator().manual_seed(5)
+    rnd = lambda *s: torch.randn(*s, generator=g).to(DEV)
+    if kind == "qmixer":       # R = 4 rows, A = 2, E = 32, 3 raw features per agent
+        net, R = QMixer(BA, 32, 3, DEV, seed=6), 4
+        obs, q, dq_tot, dq = rnd(R * BA, 3), rnd(R, BA), rnd(R), torch.empty(R, BA, device=DEV)
+
+        def run():
+            net.apply(obs, 3, R, q, train=True)
+            net.bwd(dq_tot, dq=dq)
+        return net, run
+    R = BNSEQ * BT * BA
+    obs, dvalue, dlogits = rnd(R, BF), rnd(R), torch.zeros(R, 64, device=DEV)
+    dlogits[:, :BK] = rnd(R, BK)
+    dones = (torch.rand(BNSEQ, BT, generator=g) < 0.3).to(torch.uint8).to(DEV)
+    if kind == "ff_actor":
+        net = FfActor(BA, BK, BF, DEV, seed=6, tuning=Tuning(), wgrad_groups=4)
+        return net, lambda: (net.apply(obs), net.bwd(dlogits))
+    if kind in ("gru_actor", "gru_critic"):
+        net = GruActor(BA, BK, BF, DEV, seed=6, tuning=Tuning(), wgrad_groups=4) if kind == "gru_actor" else \
+            GruCritic(BA, BF, DEV, seed=6, tuning=Tuning(), wgrad_groups=4)
+        h0, h0_idx = rnd(BNSEQ * BA, 128), torch.arange(BNSEQ * BA, dtype=torch.int32, device=DEV)
+        return net, lambda: (net.seq_fwd(obs, dones, h0, h0_idx, BNSEQ, BT), net.seq_bwd(dlogits if kind == "gru_actor" else dvalue))
+    net = SableGuider(BA, BK, BF, DEV, embed_dim=int(kind[len("sable"):]), max_pos=4, seed=6, tuning=Tuning(), wgrad_groups=4)
+    prev = torch.randint(0, BK + 1, (R,), generator=g, dtype=torch.int32).to(DEV)
+    pos = torch.randint(0, 4, (R,), generator=g, dtype=torch.int32).to(DEV)
+    s0 = tuple(0.1 * rnd(net.nb, net.ntile, BNSEQ, 64, 64) for _ in range(3))
+    seq_env = torch.arange(BNSEQ, dtype=torch.int32, device=DEV)
+    return net, lambda: (net.train_fwd(obs, prev, pos, dones, s0, seq_env, BNSEQ, BT), net.train_bwd(dlogits, dvalue))
+
+
+@pytest.mark.parametrize("kind", ["gru_actor", "gru_critic", "ff_actor", "sable64", "sable32", "qmixer"])
+def test_bind_grads_sends_the_next_backward_to_the_new_buffer_and_leaves_the_old_one(kind):
+    """After ``bind_grads`` the same forward / backward writes the same gradients, bit for bit (no atomics in these kernels), into the new
+    buffer -- pre-filled with NaN, so an entry the backward left to the old buffer would show -- and not one element of the old buffer,
+    which holds NaN as its sentinel.  sable32 is the embedded network: the kernels write ``grads_D``, a buffer of the device width that
+    stays the network's own, and ``emb.fold`` must land in the new logical buffer.
+
+    "Every entry" is every entry a backward writes.  None writes the padding behind an entry (entries start at multiples of 4 floats), and
+    the guider's none writes the gradients of the SwiGLU weights: the HIP path keeps those weights at their zero init
+    (SableGuider.check_ffn_zero), their gradients are exactly 0 and stay what the buffer held -- the learners bind zero-filled buffers."""
+    net, run = _bind_case(kind)
+    run()
+    torch.cuda.synchronize()
+    first, old = net.grads.clone(), net.grads
+    written = torch.zeros(net.P.numel, dtype=torch.bool, device=DEV)
+    for n, v in net.P.views(written).items():
+        v.fill_(".ffn." not in n)
+    new = torch.full_like(first, float("nan"))
+    net.bind_grads(new)
+    old.fill_(float("nan"))
+    lo, hi = new.data_ptr(), new.data_ptr() + 4 * new.numel()
+    assert net.grads is new and all(lo <= v.data_ptr() < hi and v.untyped_storage().data_ptr() == new.untyped_storage().data_ptr()
+                                    for v in net.named_grads.values())
+    run()
+    torch.cuda.synchronize()
+    nan_new, nan_old = int(torch.isnan(new[written]).sum()), int(torch.isnan(old).sum())
+    print(f"BINDGRADS {kind}: {int(written.sum())} of {new.numel()} entries written by a backward; NaN left among them {nan_new}; "
+          f"old buffer still NaN in {nan_old} of {old.numel()}; bit-equal {torch.equal(new[written], first[written])}")
+    assert torch.equal(new[written], first[written])
+    assert nan_new == 0
+    assert nan_old == old.numel()
