@@ -215,6 +215,18 @@ int magpo_resnorm_fwd(const float* a, int lda, const float* y, int ldy, const fl
 int magpo_resnorm_bwd(const float* a, int lda, const float* y, int ldy, const float* s1, const float* s2,
                       const float* d0, int ldd0, const float* d1, int ldd1, const float* d2, int ldd2,
                       float* dsum, int lddsum, float* slab_s1, float* slab_s2, long R, int E, magpo_stream_t stream);
+/* residual + flax nn.LayerNorm (mat_network.py:65-66,80,85,99,108,135-137,197): out = LayerNorm(x) * scale + bias over rows of E floats,
+ * epsilon 1e-6; x = a + y (a nullable: plain LayerNorm of y) with act 0, x = gelu(y) (tanh form; a must be null) with act 2.  The
+ * statistics run over the first nf columns (1 <= nf <= E; the columns beyond are read as zero and leave as bias: a LayerNorm over nf raw
+ * features inside a zero-padded row; scale and bias always hold E floats).  bwd recomputes the statistics: dsum = d(a + y) (act 2: dy)
+ * of the incoming d0 [+ d1], slab_scale / slab_bias [magpo_row_grid(R)][E] = per-workgroup column sums of d * xhat / d (for
+ * magpo_reduce_slabs).  Strides multiples of 4 and >= E.  gelu_bwd: dz = dy gelu'(z) on rows of E floats. */
+int magpo_resln_fwd(const float* a, int lda, const float* y, int ldy, const float* scale, const float* bias, float* out, int ldout,
+                    long R, int E, int nf, int act, magpo_stream_t stream);
+int magpo_resln_bwd(const float* a, int lda, const float* y, int ldy, const float* scale, const float* d0, int ldd0, const float* d1,
+                    int ldd1, float* dsum, int lddsum, float* slab_scale, float* slab_bias, long R, int E, int nf, int act,
+                    magpo_stream_t stream);
+int magpo_gelu_bwd(const float* z, int ldz, const float* dy, int lddy, float* dz, int lddz, long R, int E, magpo_stream_t stream);
 int magpo_headmid_fwd(const float* hpre, int ldh, const float* s, float* hn, int ldhn, const float* w,
                       const float* b, float* value, int value_stride, long R, int E, magpo_stream_t stream);
 int magpo_headmid_bwd(const float* hpre, int ldh, const float* s, const float* dhn, int lddhn, const float* w,
@@ -268,6 +280,20 @@ int magpo_team_retention_fwd(const float* q, long ldq, const float* k, long ldk,
 int magpo_team_retention_bwd(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, const float* dr, long lddr,
                              float* dq, long lddq, float* dk, long lddk, float* dv, long lddv, long nteams, int A, int masked,
                              int hs, magpo_stream_t stream);
+
+/* ---- softmax attention over independent teams (attention.py:50-77 between the projections): the Multi-Agent Transformer ----
+ * The team layout of magpo_team_retention_*: nteams teams of A consecutive token rows (1 <= A <= 32); one thread per (team, row, head),
+ * sums in fp64 on the vector ALU and one fp32 rounding per output; nh heads of hs in {16, 32, 64} channels, head n at columns n hs .. of
+ * the q / k / v / y rows; q, k, v separate pointers with their own row strides (multiples of 4 floats, >= nh hs).  P = softmax_j((q_i . k_j) / sqrt(hs) + mask), y = P v, masked: j <= i
+ * only (masked pairs weigh exactly 0; the row maximum is subtracted).  ntok / ret_from as above: only rows ret_from <= i < ntok are
+ * produced, from the k / v rows j < ntok.  fwd also writes lse [R][nh] = log sum_j exp(s_ij) for the rows it produces.
+ * bwd recomputes P from q, k and lse (no [A][A] matrix in memory): dv = P^T dy, dS = P o (dy v^T - rowsum(P o dy v^T)) (the row sum
+ * equals rowsum(dy o y)), dq = dS k / sqrt(hs), dk = dS^T q / sqrt(hs), every row of every team. */
+int magpo_team_attention_fwd(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, float* y, long ldy,
+                             float* lse, long nteams, int A, int ntok, int ret_from, int masked, int hs, int nh, magpo_stream_t stream);
+int magpo_team_attention_bwd(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, const float* lse,
+                             const float* dy, long lddy, float* dq, long lddq, float* dk, long lddk, float* dv, long lddv,
+                             long nteams, int A, int masked, int hs, int nh, magpo_stream_t stream);
 
 /* ---- K2 fused acting step: SableNetwork.get_actions (sable_network.py:443-482; decode.py:111-153) in ONE launch ----
  * dims_host[16] = {N, A, K, F, n_block, n_head, hs, gs, npos, value_only, obs row stride (>= F), envs per wave (0 = by size, or 4 / 8 / 16),

@@ -568,6 +568,113 @@ template <int W> __global__ __launch_bounds__(256) void k_resnorm_bwd(ResNormBwd
 }
 
 // ------------------------------------------------------------------------------------------------
+// Residual + LayerNorm with scale and bias (flax nn.LayerNorm, epsilon 1e-6; mat_network.py:65-66, 80, 85, 99, 108, 135-137, 197):
+//   x = a + y (a nullable), or act 2: x = gelu(y) ; xhat = (x - mean(x)) rsqrt(var(x) + eps) ; out = xhat * scale + bias
+// with the statistics over the first nf <= W columns of the row (columns beyond nf are read as zero and leave as bias: the leading
+// LayerNorm of the observation encoder over F raw features inside a zero-padded row).
+// backward: g = (d0 + d1) * scale ; dx = rstd (g - mean(g) - xhat mean(g xhat)) ; dsum = dx, or act 2: dx gelu'(y) ; slabs of d * xhat
+// (scale) and d (bias).  GELU here is tanhf-exact (the rows are few: the heads, the embeddings), not common.hpp's hardware-exp form.
+__device__ __forceinline__ float gelu_tanhf(float x) { return 0.5f * x * (1.0f + tanhf(0.7978845608028654f * (x + 0.044715f * x * x * x))); }
+__device__ __forceinline__ float gelu_tanhf_grad(float x) {
+  const float c = 0.7978845608028654f, x2 = x * x, t = tanhf(c * (x + 0.044715f * x * x2));
+  return 0.5f * (1.0f + t) + 0.5f * x * (1.0f - t * t) * (c * (1.0f + 3.0f * 0.044715f * x2));
+}
+struct LnFwd { float4 xhat; float rstd; };
+// block_store_colsum with fp64 accumulators: one fp32 rounding per slab entry
+__device__ __forceinline__ void colsum_add(double (&acc)[4], float4 v) { acc[0] += v.x; acc[1] += v.y; acc[2] += v.z; acc[3] += v.w; }
+template <int W> __device__ __forceinline__ void block_store_colsum64(double (&acc)[4], float* __restrict__ outw, double* lds /*[4][W]*/) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if (W == 64) acc[i] += __shfl_xor(acc[i], 16, 64);
+    acc[i] += __shfl_xor(acc[i], 32, 64);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane < W / 4)
+    for (int i = 0; i < 4; ++i) lds[wave * W + 4 * lane + i] = acc[i];
+  __syncthreads();
+  if (threadIdx.x < W) outw[threadIdx.x] = (float)((lds[threadIdx.x] + lds[W + threadIdx.x]) + (lds[2 * W + threadIdx.x] + lds[3 * W + threadIdx.x]));
+}
+// m: 1 for the lane's columns < nf, else 0; inv = 1 / nf
+template <int W> __device__ __forceinline__ LnFwd ln_fwd(float4 x, float4 m, float inv) {
+  const float mu = rowsum<W>(f4sum(f4mul(x, m))) * inv;
+  const float4 c = f4mul(make_float4(x.x - mu, x.y - mu, x.z - mu, x.w - mu), m);
+  LnFwd o;
+  o.rstd = rsqrtf(rowsum<W>(f4sum(f4mul(c, c))) * inv + NORM_EPS);
+  o.xhat = f4scale(c, o.rstd);
+  return o;
+}
+__device__ __forceinline__ float4 ln_colmask(int c4, int nf) {
+  return make_float4(c4 < nf ? 1.f : 0.f, c4 + 1 < nf ? 1.f : 0.f, c4 + 2 < nf ? 1.f : 0.f, c4 + 3 < nf ? 1.f : 0.f);
+}
+struct ResLnArgs {
+  const float* a; const float* y; int lda, ldy;
+  const float* scale; const float* bias;          // bias: forward only
+  float* out; int ldout;                          // forward
+  const float* d0; const float* d1; int ldd0, ldd1; float* dsum; int lddsum; float* slab_scale; float* slab_bias;   // backward
+  long R; int nf, act;
+};
+template <int W> __device__ __forceinline__ float4 resln_x(const ResLnArgs& p, long row, int c4, float4& yv) {
+  yv = ld4(p.y + row * p.ldy + c4);
+  if (p.act == 2) return make_float4(gelu_tanhf(yv.x), gelu_tanhf(yv.y), gelu_tanhf(yv.z), gelu_tanhf(yv.w));
+  return p.a ? f4add(yv, ld4(p.a + row * p.lda + c4)) : yv;
+}
+template <int W> __global__ __launch_bounds__(256) void k_resln_fwd(ResLnArgs p) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c4 = 4 * (lane & (RowGeo<W>::LPR - 1));
+  const float4 sc = ld4(p.scale + c4), bi = ld4(p.bias + c4), m = ln_colmask(c4, p.nf);
+  const float inv = 1.0f / (float)p.nf;
+  for (long base = (long)blockIdx.x * RowGeo<W>::RPB; base < p.R; base += (long)gridDim.x * RowGeo<W>::RPB) {
+    const long row = base + wave * RowGeo<W>::RPW + lane / RowGeo<W>::LPR;
+    const bool ok = row < p.R;
+    float4 x = f4zero(), yv;
+    if (ok) x = resln_x<W>(p, row, c4, yv);
+    const LnFwd n = ln_fwd<W>(x, m, inv);
+    if (ok) st4(p.out + row * p.ldout + c4, f4add(f4mul(n.xhat, sc), bi));
+  }
+}
+template <int W> __global__ __launch_bounds__(256) void k_resln_bwd(ResLnArgs p) {
+  __shared__ double lds[4 * W];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c4 = 4 * (lane & (RowGeo<W>::LPR - 1));
+  const float4 sc = ld4(p.scale + c4), m = ln_colmask(c4, p.nf);
+  const float inv = 1.0f / (float)p.nf;
+  double dsc[4] = {0., 0., 0., 0.}, dbi[4] = {0., 0., 0., 0.};   // column sums in fp64 up to the slab: the fp32 roundings left are the fold's
+  for (long base = (long)blockIdx.x * RowGeo<W>::RPB; base < p.R; base += (long)gridDim.x * RowGeo<W>::RPB) {
+    const long row = base + wave * RowGeo<W>::RPW + lane / RowGeo<W>::LPR;
+    const bool ok = row < p.R;
+    float4 x = f4zero(), d = f4zero(), yv = f4zero();
+    if (ok) {
+      x = resln_x<W>(p, row, c4, yv);
+      d = ld4(p.d0 + row * p.ldd0 + c4);
+      if (p.d1) d = f4add(d, ld4(p.d1 + row * p.ldd1 + c4));
+    }
+    const LnFwd n = ln_fwd<W>(x, m, inv);
+    const float4 g = f4mul(f4mul(d, sc), m);
+    const float mg = rowsum<W>(f4sum(g)) * inv, mgx = rowsum<W>(f4sum(f4mul(g, n.xhat))) * inv;
+    colsum_add(dsc, f4mul(d, n.xhat));   // (d = 0 on rows beyond R)
+    colsum_add(dbi, d);
+    float4 dx = f4scale(f4mul(make_float4(g.x - mg - n.xhat.x * mgx, g.y - mg - n.xhat.y * mgx, g.z - mg - n.xhat.z * mgx,
+                                          g.w - mg - n.xhat.w * mgx), m), n.rstd);
+    if (p.act == 2) dx = f4mul(dx, make_float4(gelu_tanhf_grad(yv.x), gelu_tanhf_grad(yv.y), gelu_tanhf_grad(yv.z), gelu_tanhf_grad(yv.w)));
+    if (ok) st4(p.dsum + row * p.lddsum + c4, dx);
+  }
+  block_store_colsum64<W>(dsc, p.slab_scale + (long)blockIdx.x * W, lds);
+  block_store_colsum64<W>(dbi, p.slab_bias + (long)blockIdx.x * W, lds);
+}
+// dz = dy gelu'(z) on rows of W floats (the MLP of a block, mat_network.py:39-45: Dense -> gelu -> Dense; z is recomputed by the caller
+// with magpo_linear act 0).
+template <int W> __global__ __launch_bounds__(256) void k_gelu_bwd(const float* __restrict__ z, int ldz, const float* __restrict__ dy, int lddy,
+                                                                   float* __restrict__ dz, int lddz, long R) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c4 = 4 * (lane & (RowGeo<W>::LPR - 1));
+  for (long base = (long)blockIdx.x * RowGeo<W>::RPB; base < R; base += (long)gridDim.x * RowGeo<W>::RPB) {
+    const long row = base + wave * RowGeo<W>::RPW + lane / RowGeo<W>::LPR;
+    if (row >= R) continue;
+    const float4 zv = ld4(z + row * ldz + c4), d = ld4(dy + row * lddy + c4);
+    st4(dz + row * lddz + c4, make_float4(d.x * gelu_tanhf_grad(zv.x), d.y * gelu_tanhf_grad(zv.y), d.z * gelu_tanhf_grad(zv.z),
+                                          d.w * gelu_tanhf_grad(zv.w)));
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Head middle: h = gelu(hpre) ; hn = rmsnorm(h) * s ; mode 0 -> out hn ; mode 1 -> value = hn . w + b
 // (sable_network.py:102-109 value head, :277-284 logit head)
 template <int W> __global__ __launch_bounds__(256) void k_headmid_fwd(const float* __restrict__ hpre, int ldh, const float* __restrict__ s,
@@ -789,6 +896,47 @@ extern "C" int magpo_resnorm_bwd(const float* a, int lda, const float* y, int ld
   ResNormBwdArgs p{a, y, lda, ldy, s1, s2, d0, d1, d2, ldd0, ldd1, ldd2, dsum, lddsum, slab_s1, slab_s2, R};
   ROW_LAUNCH(k_resnorm_bwd, p)
   return check_launch("magpo_resnorm_bwd");
+}
+
+static int check_resln(const char* what, const ResLnArgs& p, bool null_arg, int ld2, int ld3, int ld4_, int E) {
+  if (int e = check_width(E)) return e;
+  if (null_arg || p.R < 0 || ((p.lda | p.ldy | ld2 | ld3 | ld4_) & 3) || p.ldy < E || ld2 < E || ld3 < E || (p.a && p.lda < E) || p.nf < 1 || p.nf > E ||
+      (p.act != 0 && p.act != 2) || (p.act == 2 && p.a)) {
+    set_error(what);
+    return MAGPO_EINVAL;
+  }
+  return MAGPO_OK;
+}
+
+extern "C" int magpo_resln_fwd(const float* a, int lda, const float* y, int ldy, const float* scale, const float* bias, float* out, int ldout,
+                               long R, int E, int nf, int act, hipStream_t st) {
+  ResLnArgs p{a, y, lda, ldy, scale, bias, out, ldout, nullptr, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, R, nf, act};
+  if (int e = check_resln("resln_fwd: y, scale, bias, out non-null; strides multiples of 4 and >= E; 1 <= nf <= E; act 0, or 2 without a",
+                          p, !y || !scale || !bias || !out, ldout, ldout, 0, E)) return e;
+  if (R == 0) return MAGPO_OK;
+  ROW_LAUNCH(k_resln_fwd, p)
+  return check_launch("magpo_resln_fwd");
+}
+
+extern "C" int magpo_resln_bwd(const float* a, int lda, const float* y, int ldy, const float* scale, const float* d0, int ldd0, const float* d1,
+                               int ldd1, float* dsum, int lddsum, float* slab_scale, float* slab_bias, long R, int E, int nf, int act,
+                               hipStream_t st) {
+  ResLnArgs p{a, y, lda, ldy, scale, nullptr, nullptr, 0, d0, d1, ldd0, ldd1, dsum, lddsum, slab_scale, slab_bias, R, nf, act};
+  if (int e = check_resln("resln_bwd: y, scale, d0, dsum, slabs non-null; strides multiples of 4 and >= E; 1 <= nf <= E; act 0, or 2 without a",
+                          p, !y || !scale || !d0 || !dsum || !slab_scale || !slab_bias || (d1 && ldd1 < E), ldd0, lddsum, d1 ? ldd1 : 0, E)) return e;
+  ROW_LAUNCH(k_resln_bwd, p)   // R = 0: one workgroup writes a zero slab
+  return check_launch("magpo_resln_bwd");
+}
+
+extern "C" int magpo_gelu_bwd(const float* z, int ldz, const float* dy, int lddy, float* dz, int lddz, long R, int E, hipStream_t st) {
+  if (int e = check_width(E)) return e;
+  if (!z || !dy || !dz || R < 0 || ((ldz | lddy | lddz) & 3) || ldz < E || lddy < E || lddz < E) {
+    set_error("gelu_bwd: z, dy, dz non-null; strides multiples of 4 and >= E");
+    return MAGPO_EINVAL;
+  }
+  if (R == 0) return MAGPO_OK;
+  ROW_LAUNCH(k_gelu_bwd, z, ldz, dy, lddy, dz, lddz, R)
+  return check_launch("magpo_gelu_bwd");
 }
 
 extern "C" int magpo_headmid_fwd(const float* hpre, int ldh, const float* s, float* hn, int ldhn, const float* w,

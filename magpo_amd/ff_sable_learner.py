@@ -50,9 +50,9 @@ class FfSableLearner(AnakinLearner):
             raise ValueError("rollout_length * num_envs must be divisible by num_minibatches")
         self.tuning = tuning if tuning is not None else (guider.tuning if guider is not None else Tuning.from_env())
         A, K, F = self.A, self.K, self.F
-        if guider is not None:
-            n_block, n_head, embed_dim = guider.nb, guider.nh, guider.EL
-        gn = FlatParams(guider_layout(int(embed_dim), F, K, int(n_block), int(n_head)), "cpu").numel
+        # the size of the parameter layout: the given network's own (a SableGuider, or another memoryless network with the same methods:
+        # magpo_amd.mat.MatNetwork), else that of the SableGuider built below
+        gn = guider.P.numel if guider is not None else FlatParams(guider_layout(int(embed_dim), F, K, int(n_block), int(n_head)), "cpu").numel
         # one contiguous buffer [gradients | loss scalars] = one all-reduce message (ff_sable.py:226-228)
         self.grad_all = torch.zeros(gn + 16, dtype=torch.float32, device=device)
         self.grad_acc = torch.zeros_like(self.grad_all) if num_groups > 1 else None
@@ -71,8 +71,9 @@ class FfSableLearner(AnakinLearner):
         self.g_opt = optim if optim is not None else ClipAdam(guider, sys)
         assert self.g_opt.net is guider
         # acting step: one magpo_ff_sable_act launch (Tuning.ff_sable_fused_act) or the kernel-by-kernel chain; the caller's functions win
-        select = guider.act_team_fused if self.tuning.ff_sable_fused_act else guider.act
-        self.sable_action_select_fn, self.sable_apply_fn = apply_fns if apply_fns is not None else (select, guider.apply)
+        if apply_fns is None:
+            apply_fns = (guider.act_team_fused if self.tuning.ff_sable_fused_act else guider.act, guider.apply)
+        self.sable_action_select_fn, self.sable_apply_fn = apply_fns
         self.sable_update_fn = update_fn if update_fn is not None else self.g_opt.update
         self.loss_out = self.grad_all[gn:gn + self.n_loss]
         # the key table of a rollout holds the A sample keys of every env step

@@ -479,3 +479,97 @@ def init_ff_from_key(named: Dict[str, torch.Tensor], net_key: np.ndarray, head_p
             put(n, _orth(key(("torso", f"Dense_{i}"), 1), tuple(named[n].shape), math.sqrt(2.0)))
             i += 1
         put("head.kernel", _orth(key(tuple(head_path), 1), tuple(named["head.kernel"].shape), head_gain))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Multi-Agent Transformer (mava/networks/mat_network.py:48-206, attention.py:29-36).  Names are the flax module paths joined by dots;
+# projections that always run together share one fused matrix (attn.w_qkv = [query | key | value], attn2.w_kv = [key | value]) and are
+# exposed under their reference names as column views.  Decoder.obs_encoder (:170-176) is never called and has no parameters.
+
+def mat_layout(E: int, F: int, K: int, nb: int = 1) -> "OrderedDict[str, Tuple[int, ...]]":
+    s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+
+    def ln(p, w=E):
+        s[p + ".scale"], s[p + ".bias"] = (w,), (w,)
+
+    def dense(p, din, dout):
+        s[p + ".kernel"], s[p + ".bias"] = (din, dout), (dout,)
+
+    def mlp(p):
+        dense(p + "mlp.layers_0", E, E)
+        dense(p + "mlp.layers_2", E, E)
+
+    e = "encoder."
+    ln(e + "obs_encoder.layers_0", F)
+    dense(e + "obs_encoder.layers_1", F, E)
+    ln(e + "ln")
+    for b in range(nb):
+        p = e + f"blocks.layers_{b}."
+        ln(p + "ln1"); ln(p + "ln2")
+        s[p + "attn.w_qkv"], s[p + "attn.b_qkv"] = (E, 3 * E), (3 * E,)
+        dense(p + "attn.proj", E, E)
+        mlp(p)
+    dense(e + "head.layers_0", E, E)
+    ln(e + "head.layers_2")
+    dense(e + "head.layers_3", E, 1)
+    d = "decoder."
+    s[d + "action_encoder.layers_0.kernel"] = (K + 1, E)
+    ln(d + "ln")
+    for b in range(nb):
+        p = d + f"cross_attention_block_{b}."
+        ln(p + "ln1"); ln(p + "ln2"); ln(p + "ln3")
+        s[p + "attn1.w_qkv"], s[p + "attn1.b_qkv"] = (E, 3 * E), (3 * E,)
+        dense(p + "attn1.proj", E, E)
+        dense(p + "attn2.query", E, E)
+        s[p + "attn2.w_kv"], s[p + "attn2.b_kv"] = (E, 2 * E), (2 * E,)
+        dense(p + "attn2.proj", E, E)
+        mlp(p)
+    dense(d + "head.layers_0", E, E)
+    ln(d + "head.layers_2")
+    dense(d + "head.layers_3", E, K)
+    return s
+
+
+def mat_named_views(views: Dict[str, torch.Tensor], E: int = 64) -> Dict[str, torch.Tensor]:
+    """Reference-named parameter dict: query / key / value kernels [E, E] and biases [E] as column views of the fused entries."""
+    out: Dict[str, torch.Tensor] = {}
+    for n, v in views.items():
+        stem, leaf = n.rsplit(".", 1)
+        if leaf in ("w_qkv", "b_qkv", "w_kv", "b_kv"):
+            names = ("query", "key", "value") if leaf.endswith("qkv") else ("key", "value")
+            for i, m in enumerate(names):
+                out[f"{stem}.{m}.{'kernel' if leaf[0] == 'w' else 'bias'}"] = v[..., i * E:(i + 1) * E]
+        else:
+            out[n] = v
+    return out
+
+
+def mat_kernel_gain(name: str) -> float:
+    """orthogonal(gain) of a Dense kernel: 0.01 for the attention projections (attention.py:31-36), the second MLP layer
+    (mat_network.py:43) and the last layer of a head (:100, :191); sqrt(2) for every other one (:41, :81, :97, :156, :188)."""
+    small = any(t in name for t in (".key.", ".query.", ".value.", ".proj.", "mlp.layers_2.", "head.layers_3."))
+    return 0.01 if small else math.sqrt(2.0)
+
+
+def init_mat(named: Dict[str, torch.Tensor], seed: int) -> None:
+    """The reference's init distributions from a torch generator, for tests and benchmarks."""
+    gen = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for name, v in named.items():
+            if name.endswith("kernel"):
+                v.copy_(_orthogonal(gen, tuple(v.shape), mat_kernel_gain(name)))
+            else:
+                v.fill_(1.0 if name.endswith("scale") else 0.0)
+
+
+def init_mat_from_key(named: Dict[str, torch.Tensor], net_key: np.ndarray) -> None:
+    """The MultiAgentTransformer parameters flax creates from ``net_key`` (mat.py:353): one key per Dense kernel from its module path and
+    creation counter 1, orthogonal with the reference's gains; ones for the LayerNorm scales, zeros for every bias.  UNPINNED like the
+    other initialisers (the samplers and flax's key derivation are restated from memory, oracle/prng.py)."""
+    with torch.no_grad():
+        for name, v in named.items():
+            if name.endswith("kernel"):
+                k = _param_key(net_key, tuple(name.split(".")[:-1]), 1)
+                v.copy_(torch.from_numpy(np.ascontiguousarray(_orth(k, tuple(v.shape), mat_kernel_gain(name)))))
+            else:
+                v.fill_(1.0 if name.endswith("scale") else 0.0)

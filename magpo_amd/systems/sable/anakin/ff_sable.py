@@ -88,9 +88,15 @@ def get_learner_fn(env, apply_fns, update_fn, config):
     ``SableGuider.act_team_fused`` (the same step in one launch),
     ``SableGuider.apply`` and ``ClipAdam.update`` of the objects that own the device buffers (or thin functools.wraps / functools.partial
     adaptors around them), and the loop CALLS exactly what it is given; anything else raises the ``TypeError`` of common._owner."""
+    return learner_fn_for(SableGuider, env, apply_fns, update_fn, config)
+
+
+def learner_fn_for(net_cls, env, apply_fns, update_fn, config):
+    """``get_learner_fn`` for the memoryless network class ``net_cls`` (SableGuider; magpo_amd.mat.MatNetwork for the mat system, whose
+    learner is this one, mava/systems/mat/anakin/mat.py:82-283)."""
     sable_action_select_fn, sable_apply_fn = apply_fns
-    guider = _owner(sable_apply_fn, SableGuider, "apply", "apply_fns[1] (sable_apply_fn)")
-    if _owner(sable_action_select_fn, SableGuider, "act", "apply_fns[0] (sable_action_select_fn)") is not guider:
+    guider = _owner(sable_apply_fn, net_cls, "apply", "apply_fns[1] (sable_apply_fn)")
+    if _owner(sable_action_select_fn, net_cls, "act", "apply_fns[0] (sable_action_select_fn)") is not guider:
         raise ValueError("the execution and the training function must belong to one Sable network")
     optim = _owner(update_fn, ClipAdam, "update", "update_fn")
     _, world = mdist.rank_world()
